@@ -6,11 +6,15 @@ Mirrors rtp_llm/test/perf_test/batch_decode_test.py + BatchDecodeScheduler
 without running prefill, every step decodes one token per sequence (greedy, fed back on
 device), W warm-up steps then K timed steps.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload NAME --batch B --ctx C]
+    python bench.py [--gpus N --steps K --warmup W] [--workload NAME --batch B --ctx C] [--dump-outputs DIR] [--full]
 
 One JSON line on stdout (rank 0): BASELINE.json's metric (decode tokens/s + p50 latency,
-Qwen2-7B W4A16, seq 1024), plus `roofline` (dominant kernel = the weight-only dequant GEMM,
-algorithmic bytes / HIP-event time) and `cpu_baseline` (the CPU oracle timed on this host).
+Qwen2-7B W4A16, seq 1024).  A plain run sets up, warms up, times the K steps and prints that line.
+--full adds the figures that take runs of their own: three more blocks of K steps (`ms_per_step_repeats`),
+`roofline` (dominant kernel = the weight-only dequant GEMM, algorithmic bytes / HIP-event time) and
+`step_roofline`, the b = 1..64 sweep, the other single-GPU workloads and prefill, and `cpu_baseline`
+(the CPU oracle timed on the same host).  --dump-outputs DIR writes what the last timed step computed
+(DIR/<name>.npy); the inputs are seeded, so two builds can be compared output for output.
 Data: synthetic (random-init weights of the named architecture, random KV) — there is no
 network for checkpoints.  N > 1 (one process per GPU, torchrun env): the headline is the tensor-parallel layout (TP degree
 = the largest valid divisor of N) with the hand-written xGMI all-reduce inside the C++ step; N independent
@@ -85,6 +89,33 @@ def fill_kv_random(eng, B, ctx, seed):
             eng.kv_scale[l].copy_(torch.rand(eng.kv_scale[l].shape, device=eng.device, generator=g) * 0.02 + 0.005)
         else:
             kv.copy_(torch.randn(kv.shape, device=eng.device, generator=g, dtype=torch.float16).to(kv.dtype))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def step_outputs(eng, B):
+    """What a caller of the timed step holds after its last step: the logits of the B rows (the rank's vocabulary shard under
+    TP), the greedy next token ids fed back to the following step, the final normed hidden state.  Device copies, no sync:
+    under TP the peers must not wait on this rank."""
+    return {"logits": eng.logits[:B].clone(), "next_token_ids": eng.token_ids[:B].clone(), "hidden": eng.hidden[:B].clone()}
+
+
+def write_outputs(d, outs):
+    """DIR/<name>.npy in float32 (token ids in float64), DUMP_BUDGET_BYTES in all: logits wider than the room left are cut to a
+    fixed, seeded sample of columns, written beside them as logits_columns.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrs = {k: v.to(torch.float64 if k == "next_token_ids" else torch.float32).cpu().numpy() for k, v in outs.items()}
+    logits = arrs["logits"]
+    room = DUMP_BUDGET_BYTES - sum(a.nbytes for k, a in arrs.items() if k != "logits") - (1 << 16)   # npy headers
+    if logits.nbytes > room:
+        ncol = max(1, room // (logits.shape[0] * 4 + 8))
+        cols = np.sort(np.random.default_rng(0).choice(logits.shape[1], ncol, replace=False))
+        arrs["logits"], arrs["logits_columns"] = np.ascontiguousarray(logits[:, cols]), cols.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    log(f"[bench] wrote {', '.join(sorted(arrs))} to {d}")
 
 
 def cpu_baseline(cfg, kind, kv_int8, B, ctx, budget_s=25.0):
@@ -211,6 +242,9 @@ def main():
     ap.add_argument("--debug-set", default="", help="debug only: 'idx=val,...' forwarded to mi355_debug_set (kernel A/B switches)")
     ap.add_argument("--attn-ps", type=int, default=0, help="debug only (tuning build): tokens per attention partition instead of the planner's choice")
     ap.add_argument("--prefetch", type=int, default=None, help="weight-prefetch mask (mi355_decoder_set_weight_prefetch); default: the engine's")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: spread blocks, roofline, batch sweep, "
+                    "other workloads + prefill, CPU baseline (--no-sweep / --no-cpu-baseline still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -310,8 +344,9 @@ def main():
         bt = torch.randperm(num_blocks, generator=torch.Generator().manual_seed(2)).reshape(B, blocks_per_seq).to(torch.int32)
         return cfg, eng, (lambda: eng.set_inputs(ids0.tolist(), [ctx - 1] * B, bt))
 
-    def timed(run, reset):
-        """W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; max over ranks."""
+    def timed(run, reset, snapshot=None):
+        """W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; max over ranks.  snapshot() keeps the
+        outputs of the last of the K steps (--dump-outputs) before the p50 pass moves on."""
         reset()
         run(args.warmup)
         torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
@@ -319,6 +354,7 @@ def main():
         run(args.steps)
         torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        outs = snapshot() if snapshot is not None else None
         # p50 step latency (separate pass, per-step events on the launch stream)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(33)]
         evs[0].record()
@@ -326,7 +362,7 @@ def main():
             run(1)
             evs[i + 1].record()
         torch.cuda.synchronize()
-        return elapsed, statistics.median(evs[i].elapsed_time(evs[i + 1]) for i in range(32))
+        return elapsed, statistics.median(evs[i].elapsed_time(evs[i + 1]) for i in range(32)), outs
 
     # ---- headline layout: every GPU is a replica of the whole model with its own `batch` sequences (decode requests
     # are independent units: no data-path collective, weak scaling).  The TP layout is measured after it.
@@ -343,21 +379,16 @@ def main():
     if not args.no_graph:
         eng.capture(B)
     run = (lambda n: eng.replay(B, n)) if not args.no_graph else (lambda n: [eng.step(B) for _ in range(n)])
-    elapsed, p50 = timed(run, reset)
+    dump = args.dump_outputs is not None and rank == 0
+    elapsed, p50, outputs = timed(run, reset, (lambda: step_outputs(eng, B)) if dump else None)
     ms_per_step = elapsed / args.steps * 1e3
     tokens_per_s = B * dp * args.steps / elapsed
-    # spread: the K timed steps are ~70 ms of device time at the driver's K = 20; three more blocks of K steps (not part of
-    # `value`) show how far one block can sit from the typical one
-    repeats = []
-    for _ in range(3):
-        torch.cuda.synchronize(); t0 = time.perf_counter(); run(args.steps); torch.cuda.synchronize()
-        repeats.append(round((time.perf_counter() - t0) / args.steps * 1e3, 4))
 
     out = {
         "metric": "decode tokens/sec + p50 latency, Qwen2-7B W4A16 b=1..64 @1/2/4/8 GPU" if args.workload == "qwen2-7b-w4a16"
                   else f"decode tokens/sec + p50 latency ({args.workload})",
         "value": round(tokens_per_s, 1), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "p50_ms": round(p50, 4), "ms_per_step_repeats": repeats, "higher_is_better": True,
+        "ms_per_step": round(ms_per_step, 4), "p50_ms": round(p50, 4), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f16",
         "data": "synthetic (random-init weights of the named architecture, random KV cache, greedy decode)",
         "config": {"workload": f"{args.workload}: {mname} decode, weights {kind}"
@@ -365,6 +396,14 @@ def main():
                    "batch": B, "global_batch": B * dp, "seq_len": ctx, "parallelism": "tp1" if dp == 1 else f"dp{dp} (one full replica per GPU, {B} sequences each)",
                    "graph": not args.no_graph},
     }
+    if args.full:
+        # spread: the K timed steps are ~70 ms of device time at the driver's K = 20; three more blocks of K steps (not part of
+        # `value`) show how far one block can sit from the typical one
+        repeats = []
+        for _ in range(3):
+            torch.cuda.synchronize(); t0 = time.perf_counter(); run(args.steps); torch.cuda.synchronize()
+            repeats.append(round((time.perf_counter() - t0) / args.steps * 1e3, 4))
+        out["ms_per_step_repeats"] = repeats
     if args.layers:
         out["invalid"] = f"debug run with --layers {args.layers}"
     if args.debug_set or args.attn_ps:
@@ -418,11 +457,11 @@ def main():
             rl["frac_kernel_time"] = round(rl["achieved_kernel_time"] / HBM_PEAK_GBS, 4)
         return rl, bps_r, prof_r
 
-    if rank == 0 and world > 1:   # N > 1: the line carries `roofline` and `cpu_baseline` too (rank 0's replica here; replaced by its TP shard below)
+    if args.full and rank == 0 and world > 1:   # N > 1: the line carries `roofline` and `cpu_baseline` too (rank 0's replica here; replaced by its TP shard below)
         out["roofline"], _, _ = roofline_of(cfg, eng, reset, out["config"]["parallelism"], False)
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg_full, kind, kv_int8, B, ctx)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # ---- roofline of the dominant kernel (weight-only dequant GEMM): algorithmic bytes / HIP-event time
         out["roofline"], bps, prof = roofline_of(cfg, eng, reset, "tp1", True)
         total_b = sum(bps.values())
@@ -493,7 +532,9 @@ def main():
     if world > 1 and not args.no_tp:
         import threading
         replica = {"parallelism": out["config"]["parallelism"], "global_batch": B * dp, "tokens_per_s": out["value"],
-                   "ms_per_step": out["ms_per_step"], "p50_ms": out["p50_ms"], "ms_per_step_repeats": out["ms_per_step_repeats"], "scaling": "weak"}
+                   "ms_per_step": out["ms_per_step"], "p50_ms": out["p50_ms"], "scaling": "weak"}
+        if args.full:
+            replica["ms_per_step_repeats"] = out["ms_per_step_repeats"]
 
         def _tp_timeout():
             if rank == 0:
@@ -565,19 +606,20 @@ def main():
                     treset(); teng.capture(B)
                 agree = ranks_agree()
             protocol = "rccl" if ar is None else HAND_OVER[ar.hand_over]
-            t_el, t_p50 = timed(trun, treset)
-            # the same three extra blocks of K steps as for the replica layout, so that `ms_per_step_repeats` of the line belongs to the
-            # layout `value` / `ms_per_step` are quoted on (max over ranks: a TP step ends when its slowest rank does)
-            t_repeats = []
-            for _ in range(3):
-                torch.cuda.synchronize(); barrier(); t0r = time.perf_counter(); trun(args.steps); torch.cuda.synchronize()
-                t_repeats.append(round(max_over_ranks(time.perf_counter() - t0r) / args.steps * 1e3, 4))
-            # roofline of the headline layout: every rank profiles its shard together (the eager steps run the in-step all-reduces)
-            tp_roof = None
-            try:
-                tp_roof, _, _ = roofline_of(tcfg, teng, treset, f"tp{tpn} (rank 0's shard)", False)
-            except Exception as e:  # noqa: BLE001
-                log(f"[rank {rank}] roofline pass of the TP layout failed ({type(e).__name__}: {e}); the line keeps the replica's")
+            t_el, t_p50, t_outputs = timed(trun, treset, (lambda: step_outputs(teng, B)) if dump else None)
+            t_repeats, tp_roof = None, None
+            if args.full:
+                # the same three extra blocks of K steps as for the replica layout, so that `ms_per_step_repeats` of the line belongs to the
+                # layout `value` / `ms_per_step` are quoted on (max over ranks: a TP step ends when its slowest rank does)
+                t_repeats = []
+                for _ in range(3):
+                    torch.cuda.synchronize(); barrier(); t0r = time.perf_counter(); trun(args.steps); torch.cuda.synchronize()
+                    t_repeats.append(round(max_over_ranks(time.perf_counter() - t0r) / args.steps * 1e3, 4))
+                # roofline of the headline layout: every rank profiles its shard together (the eager steps run the in-step all-reduces)
+                try:
+                    tp_roof, _, _ = roofline_of(tcfg, teng, treset, f"tp{tpn} (rank 0's shard)", False)
+                except Exception as e:  # noqa: BLE001
+                    log(f"[rank {rank}] roofline pass of the TP layout failed ({type(e).__name__}: {e}); the line keeps the replica's")
             st = ar.status() if ar is not None else 0
             if st != 0:
                 raise RuntimeError(f"all-reduce spin timed out (status {st})")
@@ -589,9 +631,12 @@ def main():
                                       ("RCCL fallback (IPC peer mapping unavailable): ncclAllReduce on the local split-K fold (2 per layer) + "
                                        "ncclAllGather of one (max, index) pair per row, all inside the captured step")}
             # headline := the TP layout
-            out.update(value=tp_info["tokens_per_s"], ms_per_step=tp_info["ms_per_step"], p50_ms=tp_info["p50_ms"], ms_per_step_repeats=t_repeats,
+            out.update(value=tp_info["tokens_per_s"], ms_per_step=tp_info["ms_per_step"], p50_ms=tp_info["p50_ms"],
                        scaling="strong" if dpn == 1 else "strong within a tp group, weak across the dp groups")
+            if t_repeats is not None:
+                out["ms_per_step_repeats"] = t_repeats
             out["config"].update(parallelism=tp_info["parallelism"], global_batch=B * dpn)
+            outputs = t_outputs
             out["tp_layout"], out["replica_layout"] = tp_info, replica
             if tp_roof is not None:
                 out["replica_layout"]["roofline"] = out.get("roofline")
@@ -601,6 +646,8 @@ def main():
             out["replica_layout"] = replica
             log(f"[rank {rank}] TP layout failed, headline stays on the replica layout: {out['tp_layout']['error']}")
         watchdog.cancel()
+    if dump:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

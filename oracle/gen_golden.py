@@ -10,7 +10,7 @@ imports of the compiled op libraries are stubbed (verified importable
   * GpuImpl.apply_int8 / symmetric_quantize_last_axis_of_batched_matrix  device_impl.py:183-222
 and record inputs + outputs.  We also execute the reference's own torch reference implementations (the functions
 its ROCm unit tests compare the native kernels against) and record their inputs + outputs in
-tests/golden/ref_layers.npz, so that oracle/oracle.py is pinned to the reference for the floating-point layer math:
+tests/golden/ref_layers.*.npz, so that oracle/oracle.py is pinned to the reference for the floating-point layer math:
   * RMSNormTorch.forward                 models_py/modules/base/common/norm.py:83-92
   * ref_masked_attention / run_native    models_py/modules/base/rocm/test/rocm_fmha_test.py:262-372
   * _torch_reference (NeoX RoPE, QKV split)  models_py/modules/factory/attention/rocm_impl/test/test_fused_qkv_transpose_v3.py:246-307
@@ -19,7 +19,7 @@ From the ROCm-packed int4 output we also recover the canonical
 codes (undoing the CK nibble permutation and column-major packing, device_impl.py:729-771)
 so tests can pin rtp_llm_amd.quant.unpack_gptq/unpack_awq bit-exactly.
 
-    python oracle/gen_golden.py            # writes tests/golden/quant_{gptq,awq,int8}.npz and ref_layers.npz
+    python oracle/gen_golden.py            # writes tests/golden/quant_{gptq,awq,int8}.npz and ref_layers.*.npz
 """
 import importlib.util
 import os
@@ -31,6 +31,16 @@ import torch
 
 REF = "/root/reference"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+# the layer pins are written one file per kernel family, so that every committed file stays under 1 MiB
+REF_PARTS = {"norm_rope": ("norm", "rope"), "attn": ("attn",), "mlp": ("mlp",)}
+
+
+def save_parts(stem, out):
+    """out -> tests/golden/<stem>.<family>.npz; tests/test_oracle_pinned.py merges them back."""
+    every = tuple(p for prefixes in REF_PARTS.values() for p in prefixes)
+    assert all(k.startswith(every) for k in out), sorted(k for k in out if not k.startswith(every))
+    for part, prefixes in REF_PARTS.items():
+        np.savez_compressed(os.path.join(OUT, f"{stem}.{part}.npz"), **{k: v for k, v in out.items() if k.startswith(prefixes)})
 
 
 class _Any:
@@ -112,7 +122,7 @@ def _rand_awq(K, N, g, seed):
 
 
 def gen_ref_layers():
-    """Run the reference's own torch reference implementations on seeded inputs -> tests/golden/ref_layers.npz."""
+    """Run the reference's own torch reference implementations on seeded inputs -> tests/golden/ref_layers.*.npz."""
     _install_stubs()
     MP = "rtp_llm/models_py/"
     norm = _load("ref_norm", MP + "modules/base/common/norm.py")
@@ -188,12 +198,12 @@ def gen_ref_layers():
     x, gate, up, down = rn(T, H, s=0.5).half(), rn(H, I, s=0.06).half(), rn(H, I, s=0.06).half(), rn(I, H, s=0.04).half()
     y = mlp.DenseMLP(gate, up, down, sys.modules["rtp_llm.ops"].ActivationType.Swiglu)(x)
     out.update(mlp_x=x.numpy(), mlp_gate=gate.numpy(), mlp_up=up.numpy(), mlp_down=down.numpy(), mlp_y=y.numpy())
-    np.savez_compressed(os.path.join(OUT, "ref_layers.npz"), **out)
+    save_parts("ref_layers", out)
 
 
 def gen_ref_layers_bf16():
     """The same reference implementations on bf16 tensors (the reference's second activation dtype) ->
-    tests/golden/ref_layers_bf16.npz; bf16 arrays are stored as their int16 bit patterns (numpy has no bf16)."""
+    tests/golden/ref_layers_bf16.*.npz; bf16 arrays are stored as their int16 bit patterns (numpy has no bf16)."""
     _install_stubs()
     MP = "rtp_llm/models_py/"
     norm = _load("ref_norm", MP + "modules/base/common/norm.py")
@@ -246,8 +256,8 @@ def gen_ref_layers_bf16():
     x, gate, up, down = rn(T, H, s=0.5).to(BF), rn(H, I, s=0.06).to(BF), rn(H, I, s=0.06).to(BF), rn(I, H, s=0.04).to(BF)
     y = mlp.DenseMLP(gate, up, down, sys.modules["rtp_llm.ops"].ActivationType.Swiglu)(x)
     out.update(mlp_x=bits(x), mlp_gate=bits(gate), mlp_up=bits(up), mlp_down=bits(down), mlp_y=bits(y))
-    np.savez_compressed(os.path.join(OUT, "ref_layers_bf16.npz"), **out)
-    print("wrote ref_layers_bf16.npz")
+    save_parts("ref_layers_bf16", out)
+    print("wrote ref_layers_bf16.*.npz")
 
 
 def main():

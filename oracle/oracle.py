@@ -13,11 +13,11 @@ this path, each function citing the reference lines it follows.  Pinning status
   * RMSNorm / NeoX RoPE / paged decode attention (fp16 KV, and per-token-scaled 8-bit KV) / SiLU-gate MLP: PINNED against
     outputs of the reference's own torch reference implementations (RMSNormTorch, _torch_reference, run_native /
     ref_masked_attention, DenseMLP -- the functions its ROCm unit tests compare the native kernels with at
-    atol=rtol=1e-2), executed unmodified by oracle/gen_golden.py -> tests/golden/ref_layers.npz, checked by
+    atol=rtol=1e-2), executed unmodified by oracle/gen_golden.py -> tests/golden/ref_layers.*.npz, checked by
     tests/test_oracle_pinned.py (bit-equal, or within one fp16 ulp where the fp32 contraction order differs).
   * The same four in bf16 (the functions are dtype-generic: fp32 math, rounding to the input dtype where the reference's tensors
     have that dtype): PINNED against the same reference implementations executed on bf16 tensors ->
-    tests/golden/ref_layers_bf16.npz (RMSNorm bit-equal; RoPE / attention within one bf16 ulp).
+    tests/golden/ref_layers_bf16.*.npz (RMSNorm bit-equal; RoPE / attention within one bf16 ulp).
   * Scaled RoPE styles (linear / llama3 / yarn): PINNED bit for bit, see rope_inv_freq and oracle/gen_rope_golden.py.
   * Dynamic-NTK RoPE (rope_dynamic_ntk_bases): "dynamic" PINNED (2e-6 relative: fp32 here and on the device, double in the torch form) against
     the reference's own torch form of the style, DeepseekV3DynamicNTKScalingRotaryEmbedding (rtp_llm/models/rotary_embedding/

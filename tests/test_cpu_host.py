@@ -365,7 +365,7 @@ def test_host_side_plans_of_the_image_launches():
 
 
 def test_committed_bench_line_and_traffic_file_follow_the_contract():
-    """profiles/r06_bench_default.json is the line `python bench.py` printed on an MI355X: the fields the driver and the judge read are
+    """profiles/r06_bench_default.json is the line `python bench.py --full` printed on an MI355X: the fields the driver and the judge read are
     there, and the static PMC traffic figure is only quoted for the kernel sources it was measured on (bench.gemm_sources_sha)."""
     import json, os, importlib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -387,7 +387,7 @@ def test_committed_bench_line_and_traffic_file_follow_the_contract():
     # round 6: the same bytes over the kernels' own durations (rocprofv3 --kernel-trace pass of tools/engine_traffic.sh), beside the eager-event fraction
     assert abs(rf["avg_kernel_us"] - tj["gemm_quant_kernel_us_per_launch"]) < 1e-2 and rf["avg_kernel_us"] < rf["avg_launch_us"]
     assert abs(rf["frac_kernel_time"] - rf["bytes_per_launch"] / rf["avg_kernel_us"] / 1e3 / rf["peak"]) < 1e-3 and rf["frac_kernel_time"] > rf["frac"]
-    # N > 1: the line carries `roofline` (the headline TP layout's shard of rank 0) and `cpu_baseline` too -- dry runs of `python bench.py --gpus N` (no
+    # N > 1: the --full line carries `roofline` (the headline TP layout's shard of rank 0) and `cpu_baseline` too -- dry runs of `python bench.py --gpus N` (no
     # launcher: bench.py starts its own ranks, round 6) with every rank on ONE GPU (timing meaningless, the fields are what is checked)
     for n in (2, 8):
         dj = json.loads(open(os.path.join(root, "profiles", f"r06_dryrun_selfspawn_{n}ranks_one_gpu.json")).read().strip().splitlines()[-1])
@@ -430,3 +430,27 @@ def test_bench_gpus_n_without_a_launcher_spawns_its_own_ranks(tmp_path):
     assert "rank 1 of 3" in ok.stderr and "rank 2 of 3" in ok.stderr
     bad = subprocess.run([sys.executable, "-c", drv], env={**env, "FAIL_RANK": "2"}, capture_output=True, text=True, timeout=120)
     assert bad.returncode == 3, (bad.returncode, bad.stderr[-500:])
+
+
+def test_bench_dump_outputs_are_float_and_within_budget(tmp_path):
+    """bench.py --dump-outputs: the last step's logits / next token ids / hidden state as float32 (ids float64) .npy files, 64 MB in
+    all; logits too wide for that are cut to the same seeded sample of columns every run, their indices written beside them."""
+    import importlib, types
+    import numpy as np
+    bench = importlib.import_module("bench")
+    for B, V, H, dt in ((64, 152064, 3584, torch.float16), (256, 152064, 3584, torch.bfloat16)):
+        eng = types.SimpleNamespace(logits=torch.randn(B + 2, V), token_ids=torch.randint(0, V, (B + 2,), dtype=torch.int32),
+                                    hidden=torch.randn(B + 2, H).to(dt))
+        runs = []
+        for i in range(2):
+            d = tmp_path / f"b{B}_{i}"
+            bench.write_outputs(str(d), bench.step_outputs(eng, B))
+            runs.append({f.stem: np.load(f) for f in sorted(d.iterdir())})
+            assert sum(f.stat().st_size for f in d.iterdir()) <= bench.DUMP_BUDGET_BYTES
+        a, b = runs
+        assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+        assert a["next_token_ids"].dtype == np.float64 and np.array_equal(a["next_token_ids"], eng.token_ids[:B].double().numpy())
+        assert a["hidden"].dtype == np.float32 and np.array_equal(a["hidden"], eng.hidden[:B].float().numpy())
+        cols = a["logits_columns"].astype(np.int64) if "logits_columns" in a else np.arange(V)
+        assert (B * V * 4 > bench.DUMP_BUDGET_BYTES) == ("logits_columns" in a)
+        assert a["logits"].dtype == np.float32 and np.array_equal(a["logits"], eng.logits[:B, cols].numpy())

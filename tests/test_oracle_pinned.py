@@ -1,6 +1,6 @@
 """Pins oracle/oracle.py to the reference for the floating-point layer math.
 
-tests/golden/ref_layers.npz holds inputs and outputs of the reference's OWN torch reference implementations,
+tests/golden/ref_layers.*.npz holds inputs and outputs of the reference's OWN torch reference implementations,
 executed unmodified from /root/reference by oracle/gen_golden.py (the functions its ROCm unit tests compare the native
 kernels against):
     RMSNormTorch                        models_py/modules/base/common/norm.py:83-92
@@ -10,6 +10,7 @@ kernels against):
 The oracle must reproduce them: bit for bit where both sides perform the same fp32 operations, and to within fp32
 re-association noise (far below one fp16 ulp of the outputs) where the contraction order differs.
 """
+import glob
 import math
 import os
 
@@ -20,9 +21,16 @@ import torch
 from oracle import oracle
 
 
+def _golden_parts(golden_dir, stem):
+    """<stem>.<family>.npz, one file per kernel family (oracle/gen_golden.py:save_parts), as one mapping."""
+    parts = sorted(glob.glob(os.path.join(golden_dir, stem + ".*.npz")))
+    assert parts, f"no {stem}.*.npz under {golden_dir}"
+    return {k: v for p in parts for k, v in np.load(p).items()}
+
+
 @pytest.fixture(scope="module")
 def ref(golden_dir):
-    return np.load(os.path.join(golden_dir, "ref_layers.npz"))
+    return _golden_parts(golden_dir, "ref_layers")
 
 
 def _t(a):
@@ -101,7 +109,7 @@ def test_mlp_reproduces_reference_dense_mlp(ref):
 # ------------------------------------------------------------------ the same pins in bf16 (the reference's second activation dtype)
 @pytest.fixture(scope="module")
 def ref_bf16(golden_dir):
-    return np.load(os.path.join(golden_dir, "ref_layers_bf16.npz"))
+    return _golden_parts(golden_dir, "ref_layers_bf16")
 
 
 def _bf(a):
@@ -109,7 +117,7 @@ def _bf(a):
 
 
 def test_bf16_oracle_reproduces_the_reference_torch_references(ref_bf16):
-    """tests/golden/ref_layers_bf16.npz: RMSNormTorch, _torch_reference (RoPE), run_native (paged attention) and DenseMLP of the
+    """tests/golden/ref_layers_bf16.*.npz: RMSNormTorch, _torch_reference (RoPE), run_native (paged attention) and DenseMLP of the
     reference executed on bf16 tensors (oracle/gen_golden.py:gen_ref_layers_bf16; arrays stored as int16 bit patterns).  The
     oracle run on the same bf16 tensors must reproduce them: this is what the bf16 HIP kernels are compared against."""
     r = ref_bf16

@@ -14,5 +14,5 @@ cd $R
 python tools/prefill_gemm_bench.py > $O/prefill_gemm_bench.txt 2>&1
 python tools/spec_bench.py > $O/spec_round.txt 2>&1
 bash tools/probe/ktrace.sh fullk python tools/fullk_bench.py --ms 1,8,64 > $O/fullk_kernel_durations.txt 2>&1
-python bench.py > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log > $O/bench_default.json
+python bench.py --full > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log > $O/bench_default.json
 ls -la $O

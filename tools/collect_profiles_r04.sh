@@ -14,5 +14,5 @@ python tools/attn_stamps.py 2>&1 | grep -v amdgpu.ids > $O/attn_stamps.txt
 python tools/batch_sweep.py 2>&1 | grep -v amdgpu.ids > $O/batch_sweep.txt
 python tools/fullk64_time.py --product --ms 64,32,16,8 2>&1 | grep -v amdgpu.ids > $O/fullk64_time.txt
 cp $O/traffic.json $R/profiles/r04_traffic.json 2>/dev/null   # so that the bench line below quotes the traffic of THESE sources
-python bench.py > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log > $O/bench_default.json
+python bench.py --full > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log > $O/bench_default.json
 ls -la $O

@@ -16,11 +16,11 @@ cd $R
 python tools/batch_sweep.py 2>&1 | grep -v amdgpu.ids > $O/batch_sweep.txt
 python tools/fullk64_time.py --product --ms 64,32,16,8 2>&1 | grep -v amdgpu.ids > $O/fullk64_time.txt
 cp $O/traffic.json $R/profiles/r05_traffic.json 2>/dev/null   # so that the bench line below quotes the traffic of THESE sources
-python bench.py > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log > $O/bench_default.json
+python bench.py --full > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log > $O/bench_default.json
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids > $O/smoke.txt
 export MI355_BENCH_ONE_GPU=1
 for n in 2 8; do
 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2973$n \
-  bench.py --gpus $n --steps 8 --warmup 2 --no-sweep > $O/dryrun_${n}ranks_one_gpu.json 2> $O/dryrun_${n}ranks.log
+  bench.py --full --gpus $n --steps 8 --warmup 2 --no-sweep > $O/dryrun_${n}ranks_one_gpu.json 2> $O/dryrun_${n}ranks.log
 done
 ls -la $O
