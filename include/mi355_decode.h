@@ -156,6 +156,11 @@ int mi355_add_rmsnorm_dt(const void* x, const float* partials, int32_t nsplit, i
                          const void* residual_in, void* residual_out, const void* weight, float eps, int32_t M, int32_t H,
                          void* y, int32_t act_dtype, mi355_stream_t stream);
 int mi355_silu_mul_dt(const void* gate_up, int32_t M, int32_t I, void* out, int32_t act_dtype, mi355_stream_t stream);
+/* Per-head QK RMSNorm (Qwen3; the leaf op of the reference's FusedQKRMSNorm, fused_qk_rmsnorm_v2), in place on packed
+ * QKV rows qkv[T][ld >= (nh + 2 nkv) hd]: every Q head with q_norm [hd], every K head with k_norm, V untouched; each head as
+ * mi355_rmsnorm_dt of one hd-wide row.  hd <= 128. */
+int mi355_qk_rmsnorm(void* qkv, int32_t T, int32_t ld, int32_t nh, int32_t nkv, int32_t hd, const void* q_norm, const void* k_norm,
+                     float eps, int32_t act_dtype, mi355_stream_t stream);
 
 int mi355_add_rmsnorm(const void* x_f16, const float* partials, int32_t nsplit, int32_t ld,
                       const void* bias, const void* residual_in, void* residual_out,
@@ -330,6 +335,18 @@ int mi355_rope_kv_write_rows(const void* qkv_f16, const float* partials, int32_t
                              const int32_t* positions, const int32_t* block_table,
                              int32_t max_blocks_per_seq, int32_t T, int32_t q_len, int32_t nh,
                              const mi355_kv_layer_t* kv, void* q_out, int32_t* oob_count, mi355_stream_t stream);
+
+/* Qwen3: the same writer with a per-head RMSNorm of every Q and K head between the bias add and the rotation -- the reference's
+ * fused_qk_rmsnorm_v2 (FusedQKRMSNorm ahead of the fmha op in CausalAttention) folded into the KV write.
+ * qkv = fp16/bf16(x W + bias); head h < nh: y = q_norm * act(x * rsqrt(mean(x^2) + eps)), nh <= h < nh + nkv: the same with
+ * k_norm (the sum of squares in fp32, q_norm / k_norm [hd] in the activation dtype, shared by all heads), rounded again, then
+ * RoPE and the KV write exactly as mi355_rope_kv_write_rows; V heads are not normed.  Other arguments as mi355_rope_kv_write_rows. */
+int mi355_rope_kv_write_rows_qk_norm(const void* qkv_f16, const float* partials, int32_t nsplit, int32_t ld,
+                                     const void* qkv_bias, const void* q_norm, const void* k_norm, float eps,
+                                     const float* cos_sin, int32_t rope_dim, int32_t max_pos,
+                                     const int32_t* positions, const int32_t* block_table,
+                                     int32_t max_blocks_per_seq, int32_t T, int32_t q_len, int32_t nh,
+                                     const mi355_kv_layer_t* kv, void* q_out, int32_t* oob_count, mi355_stream_t stream);
 
 /*
  * Paged decode attention (flash-decoding, split over the sequence) — replaces
@@ -612,6 +629,12 @@ int    mi355_decoder_prefill(mi355_decoder_t* d, const int32_t* token_ids, const
  * table.  The reference's context_rope (bindings/common/kernels/rotary_position_embedding.h:1000-1025) gives every token of a prefill batch the base of the
  * batch's longest prompt (fused_rope_kvcache_kernel.cu:219-260), while decode uses the base of each position (the model's table). */
 int    mi355_decoder_set_prefill_rope_table(mi355_decoder_t* d, const float* cos_sin);
+/* Qwen3 dense models: per-head RMSNorm of Q and K before RoPE (fused_qk_rmsnorm_v2).  q_norm / k_norm: one device
+ * pointer per layer to [hd] weights in the activation dtype (the arrays themselves are copied).  Call once, before the first step,
+ * prefill or capture; afterwards (or with a null entry) MI355_ERR_ARG.  With the norms set the QKV half of every layer is split-K
+ * mi355_linear_partial + mi355_rope_kv_write_rows_qk_norm (decode, verify rows, prefill): the fused QKV launches are switched off,
+ * since each of their blocks / epilogue jobs owns 32 of a head's hd columns and no job sees the whole head. */
+int    mi355_decoder_set_qk_norm(mi355_decoder_t* d, const void* const* q_norm, const void* const* k_norm);
 
 /* hipGraph: capture one full step for batch B on an internal stream, then replay
  * `nsteps` times back-to-back on `stream` (greedy feedback stays on device). */

@@ -89,6 +89,9 @@ SIGNATURES = {
     "mi355_embedding": (i32, [vp, i32, vp, i32, i32, vp, vp]),
     "mi355_rope_kv_write": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, C.POINTER(KVLayer), vp, vp, vp]),
     "mi355_rope_kv_write_rows": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, C.POINTER(KVLayer), vp, vp, vp]),
+    "mi355_rope_kv_write_rows_qk_norm": (i32, [vp, vp, i32, i32, vp, vp, vp, f32, vp, i32, i32, vp, vp, i32, i32, i32, i32,
+                                                 C.POINTER(KVLayer), vp, vp, vp]),
+    "mi355_qk_rmsnorm": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, f32, i32, vp]),
     "mi355_linear_residual": (i32, [vp, i32, C.POINTER(Weight), vp, vp, vp, vp, i32, vp]),
     "mi355_norm_linear": (i32, [vp, i32, C.POINTER(FusedNorm), C.POINTER(Weight), vp, vp, i32, vp]),
     "mi355_act_image_bytes": (sz, [i32, i32]),
@@ -152,6 +155,7 @@ SIGNATURES = {
     "mi355_decoder_prefill_workspace_bytes": (sz, [vp, i32, i32]),
     "mi355_decoder_prefill": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
     "mi355_decoder_set_prefill_rope_table": (i32, [vp, vp]),
+    "mi355_decoder_set_qk_norm": (i32, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "mi355_decoder_capture": (i32, [vp, i32]),
     "mi355_decoder_replay": (i32, [vp, i32, i32, vp]),
     "mi355_decoder_profile": (i32, [vp, i32, i32, C.POINTER(f32), C.POINTER(i32), vp]),

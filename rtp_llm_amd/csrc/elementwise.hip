@@ -475,3 +475,43 @@ extern "C" int mi355_argmax_pick(const void* pairs_all, int32_t world, int32_t B
     MI355_CHECK_LAUNCH("argmax_pick");
     return MI355_OK;
 }
+
+// ---------------------------------------------------------------- per-head QK RMSNorm (Qwen3)
+// The leaf op of the reference's FusedQKRMSNorm module (fused_qk_rmsnorm_v2), in place on the packed QKV rows
+// [T][ld >= (nh + 2 nkv) hd]: each Q head y = q_norm * act(x * rsqrt(mean(x^2) + eps)), each K head the same with k_norm, V
+// untouched -- the arithmetic of mi355_rmsnorm per head.  One wave per (token, head), lane i holds elements i and i + 64.
+// The decode step does not launch this: mi355_rope_kv_write_rows_qk_norm applies the same norm inside the KV writer.
+namespace {
+template <bool BF>
+__global__ __launch_bounds__(256) void qk_rmsnorm_kernel(uint16_t* __restrict__ qkv, int T, int ld, int nh, int nkv, int hd,
+                                                         const uint16_t* __restrict__ q_norm, const uint16_t* __restrict__ k_norm,
+                                                         float eps) {
+    const int t = blockIdx.x, lane = threadIdx.x & 63;
+    const int h = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (h >= nh + nkv) return;                                  // wave-uniform
+    uint16_t* row = qkv + (size_t)t * ld + (size_t)h * hd;
+    const uint16_t* w = h < nh ? q_norm : k_norm;
+    const bool a0 = lane < hd, a1 = lane + 64 < hd;
+    const float x0 = a0 ? act_from_bits<BF>(row[lane]) : 0.f, x1 = a1 ? act_from_bits<BF>(row[lane + 64]) : 0.f;
+    const float rs = rsqrtf(wave_sum(x0 * x0 + x1 * x1) / (float)hd + eps);
+    if (a0) row[lane] = act_to_bits<BF>(act_from_bits<BF>(w[lane]) * act_round<BF>(x0 * rs));
+    if (a1) row[lane + 64] = act_to_bits<BF>(act_from_bits<BF>(w[lane + 64]) * act_round<BF>(x1 * rs));
+}
+} // namespace
+
+extern "C" int mi355_qk_rmsnorm(void* qkv, int32_t T, int32_t ld, int32_t nh, int32_t nkv, int32_t hd, const void* q_norm,
+                                const void* k_norm, float eps, int32_t act_dtype, mi355_stream_t stream) {
+    MI355_CHECK_ARG(qkv && q_norm && k_norm, "qk_rmsnorm: null pointer");
+    MI355_CHECK_ARG(T > 0 && nh > 0 && nkv > 0 && hd > 0 && hd <= 128 && ld >= (nh + 2 * nkv) * hd && eps >= 0.f,
+                    "qk_rmsnorm: T=%d ld=%d nh=%d nkv=%d hd=%d (hd <= 128, ld >= (nh + 2 nkv) hd)", T, ld, nh, nkv, hd);
+    MI355_CHECK_ARG(act_dtype == MI355_ACT_F16 || act_dtype == MI355_ACT_BF16, "qk_rmsnorm: act_dtype=%d", act_dtype);
+    const dim3 grid(T, cdiv(nh + nkv, 4));
+    if (act_dtype == MI355_ACT_BF16)
+        hipLaunchKernelGGL(qk_rmsnorm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (uint16_t*)qkv, T, ld, nh, nkv, hd,
+                           (const uint16_t*)q_norm, (const uint16_t*)k_norm, eps);
+    else
+        hipLaunchKernelGGL(qk_rmsnorm_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (uint16_t*)qkv, T, ld, nh, nkv, hd,
+                           (const uint16_t*)q_norm, (const uint16_t*)k_norm, eps);
+    MI355_CHECK_LAUNCH("qk_rmsnorm_kernel");
+    return MI355_OK;
+}

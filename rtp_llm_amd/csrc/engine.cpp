@@ -111,6 +111,10 @@ struct mi355_decoder {
     void*  xg_img;                    // image of gamma 2^-e h'
     float* ssq64;                     // [64][hidden / 16 rounded up to 4]
     float* ssq;      // [16 rows][hidden / 16]: the producer GEMM's per-tile sums of h^2, consumed by the next GEMM's on-the-fly RMSNorm
+    // Qwen3 (mi355_decoder_set_qk_norm): per-layer [hd] weights of the per-head Q / K RMSNorm, empty for Qwen2 / Llama.  Set, the QKV
+    // half of every layer is split-K + mi355_rope_kv_write_rows_qk_norm: the fused QKV launches (fuse_qkv, img_qkv, tp_img_qkv) are off
+    std::vector<const void*> q_norm, k_norm;
+    bool   started;   // a step, prefill or capture has been enqueued: the launch plan is fixed
     // graphs
     hipStream_t                    cap_stream;
     std::map<int, hipGraphExec_t>  graphs;
@@ -211,6 +215,108 @@ extern "C" size_t mi355_decoder_workspace_bytes(const mi355_model_config_t* cfg)
     return carve_all(nullptr, *cfg, nullptr);
 }
 
+namespace {
+// Which launches serve which step heights, decided from the config and the weight formats (mi355_decoder_create) and again when
+// mi355_decoder_set_qk_norm takes the fused QKV launches away; the flags that depend on those (fuse_norm, fuse_rows, tp_fuse_rows,
+// tp_pub_o) follow.  The result is the mix an INT8-KV config runs: composed QKV reading xn, image O / gate_up / down at 5-64 rows.
+int plan_launches(mi355_decoder* d) {
+    const mi355_model_config_t& c = d->cfg;
+    const bool bf_act = c.act_dtype == MI355_ACT_BF16;
+    // QKV + RoPE + KV write in one launch: a 16-bit cache of the activation dtype (INT8 caches keep the quantising writer of rope_kv.hip)
+    // (not with the per-head QK norm of Qwen3: a fused QKV launch's block / epilogue job owns 32 of a head's hd columns, the norm needs the whole head)
+    const bool qkn = !d->q_norm.empty();
+    d->fuse_qkv = c.kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && c.rope_dim == c.hd && !qkn;
+    d->fuse_o = d->fuse_down = c.tp_size == 1;
+    // crossover between the few-row full-K launches (gemm_fullk.hip, dense activation loads) and the launches on activation images
+    // (round 4, same box: b = 4 1.94 vs 2.05 ms, b = 5 2.16 vs 2.05, b = 8 2.28 vs 2.07, b = 12 2.64 vs 2.10; profiles/r04_batch_sweep_crossover.txt);
+    // without the image path (other weight formats, bf16, TP) the round-3 crossover to the staged kernels stays
+    d->fuse_rows = 12;
+   // tuning build: crossover experiments (tools/batch_sweep.py --tune 6=N)
+    // W4 layers only: for small fp16 models (the 0.5B draft of speculative decoding: 36-56 blocks per launch) the fused
+    // launches measured behind the staged kernels (draft step 1.11 vs 1.05 ms), although the kernels take fp16 weights
+    auto w4ok = [](const mi355_weight_t* w) { return w->wbits == 4 && mi355_fullk_weight_ok(w); };
+    for (const auto& L : d->layers) {
+        d->fuse_qkv = d->fuse_qkv && w4ok(&L.qkv);
+        d->fuse_o = d->fuse_o && w4ok(&L.o);
+        d->fuse_down = d->fuse_down && w4ok(&L.down);
+    }
+    // the norm launches disappear as well when every GEMM of the small-batch layer is a full-K launch: O / down leave the
+    // per-tile sums of squares of the new residual rows, QKV / gate_up rebuild 1 / rms from them and normalise on load
+    d->fuse_norm = d->fuse_qkv && d->fuse_o && d->fuse_down && c.hidden % 64 == 0;
+    for (const auto& L : d->layers) d->fuse_norm = d->fuse_norm && w4ok(&L.gate_up);
+    // the 17-64-row full-K launches: W4 group-wise, K <= 5760 (gemm_fullk64.hip), single rank
+    // (either activation dtype: the images are fp16, the epilogues store the step's dtype -- the few-row launches above are fp16 only,
+    // mi355_fullk_weight_ok)
+    auto w64ok = [&](const mi355_weight_t* w) { return mi355_fullk64_weight_ok(w) != 0; };   // the launchers' own predicate (gemm.hip)
+    d->img_qkv = c.kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && c.rope_dim == c.hd && c.tp_size == 1 && !qkn;
+    d->img_o = c.tp_size == 1;
+    for (const auto& L : d->layers) { d->img_qkv = d->img_qkv && w64ok(&L.qkv); d->img_o = d->img_o && w64ok(&L.o); }
+    d->tp_img_qkv = c.tp_size > 1 && c.kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && c.rope_dim == c.hd && c.hidden % 32 == 0 && !qkn &&
+                    c.max_batch >= 1 && TUNE(5) != 2;
+    for (const auto& L : d->layers) d->tp_img_qkv = d->tp_img_qkv && mi355_fullk64_qkv_ok(&L.qkv, c.hd) != 0;
+    d->tp_img_down = c.tp_size > 1 && c.inter % 32 == 0 && TUNE(5) != 4 && TUNE(5) != 2;
+    for (const auto& L : d->layers)
+        d->tp_img_down = d->tp_img_down && L.down.K % 128 == 0 && L.down.K_pad == L.down.K && L.down.K == c.inter && L.gate_up.N == 2 * c.inter &&
+                         mi355_gemm_splitk64_plan(64, L.down.N_pad / 16, L.down.K_pad / 128, L.down.wbits, L.down.group_size, kMaxSplits, nullptr) > 0;
+    d->tp_img_gate = d->tp_img_down && c.hidden % 32 == 0 && TUNE(5) != 3;
+    for (const auto& L : d->layers)
+        d->tp_img_gate = d->tp_img_gate && L.gate_up.K % 128 == 0 && L.gate_up.K_pad == L.gate_up.K &&
+                         mi355_gemm_splitk64_direct_plan(64, L.gate_up.N_pad / 16, L.gate_up.K_pad / 128, L.gate_up.wbits, L.gate_up.group_size) > 0;
+    d->tp_pub_o = d->tp_img_qkv && !(TUNE(8) & 1);
+    d->tp_pub_down = d->tp_img_down && !(TUNE(8) & 2);
+    for (const auto& L : d->layers) {
+        d->tp_pub_o = d->tp_pub_o && mi355_fullk64_publish_ok(&L.o) != 0;
+        // down: where K stays inside two or three chunks per wave (K <= 5760: tp 4 of Qwen2-7B, tp 8 of the 70B models); deeper shards keep the K quarters
+        d->tp_pub_down = d->tp_pub_down && mi355_fullk64_publish_ok(&L.down) != 0 && (L.down.K_pad / 128 <= 45 || (TUNE(8) & 4));
+    }
+    // from how many rows the TP step takes the image launches: with the down shard as K quarters they win from ONE row (one rank of tp 2,
+    // b = 1 / 2 / 4: 1.67 / 1.68 / 1.72 ms against 1.75 / 1.77 / 1.82 with the few-row QKV launch + 15 staged slabs; profiles/r05_tp_small_batch_crossover.txt);
+    // without that plan the few-row QKV launch keeps its rows (the tp = 1 crossover)
+    d->tp_fuse_rows = (bf_act || !d->fuse_qkv || d->tp_img_down) ? 0 : 4;
+    if (TUNE(6) > 0) d->tp_fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: crossover experiments
+    if (TUNE(5) == 2) d->img_qkv = d->img_o = false;   // tuning build: A/B against the split-K + fold launches
+    // bf16 / W8: no few-row full-K launches to cross over to (gemm_fullk.hip takes fp16 steps of W4 / fp16 weights; the staged kernels lose
+    // at every height): the image launches serve 1-64 rows
+    if (d->img_qkv && d->img_o) d->fuse_rows = (bf_act || !(d->fuse_qkv && d->fuse_o && d->fuse_down)) ? 0 : 4;
+    if (TUNE(6) > 0) d->fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: crossover experiments (tools/batch_sweep.py --tune 6=N)
+    d->img_gate_up = d->img_o && c.hidden % 64 == 0 && TUNE(5) != 3;
+    for (const auto& L : d->layers) d->img_gate_up = d->img_gate_up && mi355_gemm_wide_direct_ok(&L.gate_up);
+    d->img_down = d->img_gate_up && c.inter % 32 == 0 && TUNE(5) != 4;
+    for (const auto& L : d->layers)
+        d->img_down = d->img_down && L.down.K % 128 == 0 && L.down.K_pad == L.down.K &&
+                      mi355_gemm_splitk64_plan(64, L.down.N_pad / 16, L.down.K_pad / 128, L.down.wbits, L.down.group_size, kMaxSplits, nullptr) > 0;
+    // bf16: the wide GEMM's image entry only exists with an image OUTPUT (gemm.hip mi355_linear_deferred_norm_img): without the
+    // K-quarter down launch that reads it, gate_up goes back to norm launch + staged kernel instead of failing every step
+    if (bf_act && !d->img_down) d->img_gate_up = false;
+    d->post_norm_exp.clear();
+    if (d->img_gate_up) {   // exponent of the deferred norm per layer: the largest |weight| of post_norm, read back once
+        std::vector<uint16_t> g(c.hidden);
+        for (const auto& L : d->layers) {
+            if (hipMemcpy(g.data(), L.post_norm, (size_t)c.hidden * 2, hipMemcpyDeviceToHost) != hipSuccess) {
+                mi355_set_error("decoder: cannot read the norm weights"); return MI355_ERR_HIP;
+            }
+            float mx = 0.f;
+            for (uint16_t b : g) {   // 16-bit pattern -> |value|
+                float v;
+                if (bf_act) { const uint32_t u = (uint32_t)(b & 0x7FFF) << 16; memcpy(&v, &u, 4); if (!(v == v)) v = INFINITY; }
+                else {
+                    const int e = (b >> 10) & 31, m = b & 1023;
+                    v = e == 0 ? ldexpf((float)m, -24) : (e == 31 ? INFINITY : ldexpf((float)(m | 1024), e - 25));
+                }
+                if (v > mx) mx = v;
+            }
+            int ex = 0;
+            while (ex < 14 && ldexpf(1.f, ex) < mx) ++ex;
+            if (!(mx < INFINITY) || ldexpf(1.f, ex) < mx) { d->img_gate_up = false; break; }   // inf / nan / beyond 2^14 in a norm weight: keep the norm launch
+            // a bf16 residual stream may exceed the fp16 range of the image: eight more binary orders of headroom (|h| < 1.6e7), paid for with
+            // precision only on elements below 2^-6 of a typical one
+            d->post_norm_exp.push_back(bf_act ? (ex + 8 > 14 ? 14 : ex + 8) : ex);
+        }
+    }
+    return MI355_OK;
+}
+} // namespace
+
 extern "C" mi355_decoder_t* mi355_decoder_create(const mi355_model_config_t* cfg, const mi355_layer_weights_t* layers,
                                                  const mi355_model_weights_t* model, const mi355_step_buffers_t* bufs) {
     if (!cfg || !layers || !model || !bufs) { mi355_set_error("decoder_create: null argument"); return nullptr; }
@@ -256,99 +362,12 @@ extern "C" mi355_decoder_t* mi355_decoder_create(const mi355_model_config_t* cfg
     d->cfg = *cfg; d->layers.assign(layers, layers + cfg->num_layers); d->model = *model; d->bufs = *bufs;
     carve_all(d, *cfg, bufs->workspace);
     d->xn = bufs->hidden; // the normed hidden state lives in the caller-visible buffer
+    d->started = false;
     d->B = 0; d->q_len = 1; d->cap_stream = nullptr; d->prof_on = false; d->ev_used = 0; d->ar = nullptr; d->vocab_offset = 0;
     d->has_ext = false; d->pairs_local = d->pairs_all = nullptr;
     d->side_stream = nullptr; d->ev_fork = d->ev_join = nullptr; d->overlap = false;
     d->pf_mask = MI355_PF_QKV_IN_FOLD; d->pf_pending = false;   // the one prefetch that needs no stream and measured positive (profiles/r04_touch_prefetch.txt)
-    const bool bf_act = cfg->act_dtype == MI355_ACT_BF16;
-    // QKV + RoPE + KV write in one launch: a 16-bit cache of the activation dtype (INT8 caches keep the quantising writer of rope_kv.hip)
-    d->fuse_qkv = cfg->kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && cfg->rope_dim == cfg->hd;
-    d->fuse_o = d->fuse_down = cfg->tp_size == 1;
-    // crossover between the few-row full-K launches (gemm_fullk.hip, dense activation loads) and the launches on activation images
-    // (round 4, same box: b = 4 1.94 vs 2.05 ms, b = 5 2.16 vs 2.05, b = 8 2.28 vs 2.07, b = 12 2.64 vs 2.10; profiles/r04_batch_sweep_crossover.txt);
-    // without the image path (other weight formats, bf16, TP) the round-3 crossover to the staged kernels stays
-    d->fuse_rows = 12;
-   // tuning build: crossover experiments (tools/batch_sweep.py --tune 6=N)
-    // W4 layers only: for small fp16 models (the 0.5B draft of speculative decoding: 36-56 blocks per launch) the fused
-    // launches measured behind the staged kernels (draft step 1.11 vs 1.05 ms), although the kernels take fp16 weights
-    auto w4ok = [](const mi355_weight_t* w) { return w->wbits == 4 && mi355_fullk_weight_ok(w); };
-    for (const auto& L : d->layers) {
-        d->fuse_qkv = d->fuse_qkv && w4ok(&L.qkv);
-        d->fuse_o = d->fuse_o && w4ok(&L.o);
-        d->fuse_down = d->fuse_down && w4ok(&L.down);
-    }
-    // the norm launches disappear as well when every GEMM of the small-batch layer is a full-K launch: O / down leave the
-    // per-tile sums of squares of the new residual rows, QKV / gate_up rebuild 1 / rms from them and normalise on load
-    d->fuse_norm = d->fuse_qkv && d->fuse_o && d->fuse_down && cfg->hidden % 64 == 0;
-    for (const auto& L : d->layers) d->fuse_norm = d->fuse_norm && w4ok(&L.gate_up);
-    // the 17-64-row full-K launches: W4 group-wise, K <= 5760 (gemm_fullk64.hip), single rank
-    // (either activation dtype: the images are fp16, the epilogues store the step's dtype -- the few-row launches above are fp16 only,
-    // mi355_fullk_weight_ok)
-    auto w64ok = [&](const mi355_weight_t* w) { return mi355_fullk64_weight_ok(w) != 0; };   // the launchers' own predicate (gemm.hip)
-    d->img_qkv = cfg->kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && cfg->rope_dim == cfg->hd && cfg->tp_size == 1;
-    d->img_o = cfg->tp_size == 1;
-    for (const auto& L : d->layers) { d->img_qkv = d->img_qkv && w64ok(&L.qkv); d->img_o = d->img_o && w64ok(&L.o); }
-    d->tp_img_qkv = cfg->tp_size > 1 && cfg->kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && cfg->rope_dim == cfg->hd && cfg->hidden % 32 == 0 &&
-                    cfg->max_batch >= 1 && TUNE(5) != 2;
-    for (const auto& L : d->layers) d->tp_img_qkv = d->tp_img_qkv && mi355_fullk64_qkv_ok(&L.qkv, cfg->hd) != 0;
-    d->tp_img_down = cfg->tp_size > 1 && cfg->inter % 32 == 0 && TUNE(5) != 4 && TUNE(5) != 2;
-    for (const auto& L : d->layers)
-        d->tp_img_down = d->tp_img_down && L.down.K % 128 == 0 && L.down.K_pad == L.down.K && L.down.K == cfg->inter && L.gate_up.N == 2 * cfg->inter &&
-                         mi355_gemm_splitk64_plan(64, L.down.N_pad / 16, L.down.K_pad / 128, L.down.wbits, L.down.group_size, kMaxSplits, nullptr) > 0;
-    d->tp_img_gate = d->tp_img_down && cfg->hidden % 32 == 0 && TUNE(5) != 3;
-    for (const auto& L : d->layers)
-        d->tp_img_gate = d->tp_img_gate && L.gate_up.K % 128 == 0 && L.gate_up.K_pad == L.gate_up.K &&
-                         mi355_gemm_splitk64_direct_plan(64, L.gate_up.N_pad / 16, L.gate_up.K_pad / 128, L.gate_up.wbits, L.gate_up.group_size) > 0;
-    d->tp_pub_o = d->tp_img_qkv && !(TUNE(8) & 1);
-    d->tp_pub_down = d->tp_img_down && !(TUNE(8) & 2);
-    for (const auto& L : d->layers) {
-        d->tp_pub_o = d->tp_pub_o && mi355_fullk64_publish_ok(&L.o) != 0;
-        // down: where K stays inside two or three chunks per wave (K <= 5760: tp 4 of Qwen2-7B, tp 8 of the 70B models); deeper shards keep the K quarters
-        d->tp_pub_down = d->tp_pub_down && mi355_fullk64_publish_ok(&L.down) != 0 && (L.down.K_pad / 128 <= 45 || (TUNE(8) & 4));
-    }
-    // from how many rows the TP step takes the image launches: with the down shard as K quarters they win from ONE row (one rank of tp 2,
-    // b = 1 / 2 / 4: 1.67 / 1.68 / 1.72 ms against 1.75 / 1.77 / 1.82 with the few-row QKV launch + 15 staged slabs; profiles/r05_tp_small_batch_crossover.txt);
-    // without that plan the few-row QKV launch keeps its rows (the tp = 1 crossover)
-    d->tp_fuse_rows = (bf_act || !d->fuse_qkv || d->tp_img_down) ? 0 : 4;
-    if (TUNE(6) > 0) d->tp_fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: crossover experiments
-    if (TUNE(5) == 2) d->img_qkv = d->img_o = false;   // tuning build: A/B against the split-K + fold launches
-    // bf16 / W8: no few-row full-K launches to cross over to (gemm_fullk.hip takes fp16 steps of W4 / fp16 weights; the staged kernels lose
-    // at every height): the image launches serve 1-64 rows
-    if (d->img_qkv && d->img_o) d->fuse_rows = (bf_act || !(d->fuse_qkv && d->fuse_o && d->fuse_down)) ? 0 : 4;
-    if (TUNE(6) > 0) d->fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: crossover experiments (tools/batch_sweep.py --tune 6=N)
-    d->img_gate_up = d->img_o && cfg->hidden % 64 == 0 && TUNE(5) != 3;
-    for (const auto& L : d->layers) d->img_gate_up = d->img_gate_up && mi355_gemm_wide_direct_ok(&L.gate_up);
-    d->img_down = d->img_gate_up && cfg->inter % 32 == 0 && TUNE(5) != 4;
-    for (const auto& L : d->layers)
-        d->img_down = d->img_down && L.down.K % 128 == 0 && L.down.K_pad == L.down.K &&
-                      mi355_gemm_splitk64_plan(64, L.down.N_pad / 16, L.down.K_pad / 128, L.down.wbits, L.down.group_size, kMaxSplits, nullptr) > 0;
-    // bf16: the wide GEMM's image entry only exists with an image OUTPUT (gemm.hip mi355_linear_deferred_norm_img): without the
-    // K-quarter down launch that reads it, gate_up goes back to norm launch + staged kernel instead of failing every step
-    if (bf_act && !d->img_down) d->img_gate_up = false;
-    if (d->img_gate_up) {   // exponent of the deferred norm per layer: the largest |weight| of post_norm, read back once
-        std::vector<uint16_t> g(cfg->hidden);
-        for (const auto& L : d->layers) {
-            if (hipMemcpy(g.data(), L.post_norm, (size_t)cfg->hidden * 2, hipMemcpyDeviceToHost) != hipSuccess) {
-                mi355_set_error("decoder_create: cannot read the norm weights"); delete d; return nullptr;
-            }
-            float mx = 0.f;
-            for (uint16_t b : g) {   // 16-bit pattern -> |value|
-                float v;
-                if (bf_act) { const uint32_t u = (uint32_t)(b & 0x7FFF) << 16; memcpy(&v, &u, 4); if (!(v == v)) v = INFINITY; }
-                else {
-                    const int e = (b >> 10) & 31, m = b & 1023;
-                    v = e == 0 ? ldexpf((float)m, -24) : (e == 31 ? INFINITY : ldexpf((float)(m | 1024), e - 25));
-                }
-                if (v > mx) mx = v;
-            }
-            int ex = 0;
-            while (ex < 14 && ldexpf(1.f, ex) < mx) ++ex;
-            if (!(mx < INFINITY) || ldexpf(1.f, ex) < mx) { d->img_gate_up = false; break; }   // inf / nan / beyond 2^14 in a norm weight: keep the norm launch
-            // a bf16 residual stream may exceed the fp16 range of the image: eight more binary orders of headroom (|h| < 1.6e7), paid for with
-            // precision only on elements below 2^-6 of a typical one
-            d->post_norm_exp.push_back(bf_act ? (ex + 8 > 14 ? 14 : ex + 8) : ex);
-        }
-    }
+    if (int e = plan_launches(d)) { delete d; return nullptr; }
     std::vector<int32_t> iota_h(cfg->max_batch);
     for (int i = 0; i < cfg->max_batch; ++i) iota_h[i] = i;
     if (hipMemset(d->oob_count, 0, 256) != hipSuccess ||
@@ -382,7 +401,7 @@ extern "C" int mi355_decoder_begin_rows(mi355_decoder_t* d, int32_t nseq, int32_
         return MI355_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    d->B = B; d->q_len = q_len;
+    d->B = B; d->q_len = q_len; d->started = true;
     const auto& c = d->cfg;
     if (d->embed_split) {   // hidden-split table: this rank's columns, then the ranks' slices side by side
         const int n = c.hidden / c.tp_size;
@@ -587,9 +606,15 @@ extern "C" int mi355_decoder_layer_attn(mi355_decoder_t* d, int32_t l, mi355_str
     } else {
         RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial(d->xn, B, &L.qkv, d->partials, kMaxSplits, st));
         if (pf & MI355_PF_O) if (int e = pf_issue(d, st, &L.o, kPfCap)) return e;          // under RoPE + attention
-        RUN(MI355_KC_ROPE_KV, mi355_rope_kv_write_rows(nullptr, d->partials, ns, L.qkv.N_pad, L.qkv_bias, d->model.cos_sin, c.rope_dim,
-                                                       c.max_pos, d->bufs.positions, d->bufs.block_table, c.max_blocks_per_seq, B,
-                                                       d->q_len, c.nh, &kv, d->q_buf, d->oob_count, st));
+        if (!d->q_norm.empty())   // Qwen3: per-head Q / K RMSNorm in the writer, between the bias add and the rotation
+            RUN(MI355_KC_ROPE_KV, mi355_rope_kv_write_rows_qk_norm(nullptr, d->partials, ns, L.qkv.N_pad, L.qkv_bias, d->q_norm[l], d->k_norm[l],
+                                                                   c.rms_eps, d->model.cos_sin, c.rope_dim, c.max_pos, d->bufs.positions,
+                                                                   d->bufs.block_table, c.max_blocks_per_seq, B, d->q_len, c.nh, &kv, d->q_buf,
+                                                                   d->oob_count, st));
+        else
+            RUN(MI355_KC_ROPE_KV, mi355_rope_kv_write_rows(nullptr, d->partials, ns, L.qkv.N_pad, L.qkv_bias, d->model.cos_sin, c.rope_dim,
+                                                           c.max_pos, d->bufs.positions, d->bufs.block_table, c.max_blocks_per_seq, B,
+                                                           d->q_len, c.nh, &kv, d->q_buf, d->oob_count, st));
         if (pf & MI355_PF_O_LATE) if (int e = pf_issue(d, st, &L.o, kPfCap)) return e;     // under attention only
     }
     // q_len > 1: rows of one sequence share a pass over its KV, causal mask inside the page walk (is_target_verify)
@@ -740,6 +765,21 @@ extern "C" int mi355_decoder_set_prefill_rope_table(mi355_decoder_t* d, const fl
     return MI355_OK;
 }
 
+// Qwen3 dense models: per-head RMSNorm of Q and K between the QKV projection and RoPE (fused_qk_rmsnorm_v2).  A setter,
+// not two more fields of mi355_layer_weights_t, so that the struct and every caller keep their layout.  The launch plan changes with it
+// (plan_launches: the fused QKV launches go), hence only before anything was enqueued.
+extern "C" int mi355_decoder_set_qk_norm(mi355_decoder_t* d, const void* const* q_norm, const void* const* k_norm) {
+    if (!d || !q_norm || !k_norm) { mi355_set_error("decoder_set_qk_norm: null argument"); return MI355_ERR_ARG; }
+    if (d->started || !d->graphs.empty()) {
+        mi355_set_error("decoder_set_qk_norm: must be called before the first step, prefill or capture"); return MI355_ERR_ARG;
+    }
+    for (int l = 0; l < d->cfg.num_layers; ++l)
+        if (!q_norm[l] || !k_norm[l]) { mi355_set_error("decoder_set_qk_norm: null weights of layer %d", l); return MI355_ERR_ARG; }
+    d->q_norm.assign(q_norm, q_norm + d->cfg.num_layers);
+    d->k_norm.assign(k_norm, k_norm + d->cfg.num_layers);
+    return plan_launches(d);
+}
+
 // ------------------------------------------------------------------ prefill
 // One chunk of nseq x q_len prompt tokens through the same weights: large-M GEMMs (gemm_prefill.hip above 128 rows), the
 // rows-mode KV writer, causal multi-row attention over the paged cache (earlier chunks of the same prompt are already
@@ -802,6 +842,7 @@ extern "C" int mi355_decoder_prefill(mi355_decoder_t* d, const int32_t* token_id
     if (need > workspace_bytes) { mi355_set_error("decoder_prefill: workspace %zu < %zu", workspace_bytes, need); return MI355_ERR_WORKSPACE; }
     hipStream_t st = (hipStream_t)stream;
     const float scale = 1.0f / sqrtf((float)c.hd);
+    d->started = true;
     if (d->embed_split) {
         const int n = c.hidden / c.tp_size;
         RUN(MI355_KC_OTHER, mi355_embedding(token_ids, T, d->model.embedding, n, d->model.vocab_full, b.tmp, st));
@@ -814,8 +855,14 @@ extern "C" int mi355_decoder_prefill(mi355_decoder_t* d, const int32_t* token_id
         const auto& L = d->layers[l];
         mi355_kv_layer_t kv = kv_of(d, l);
         RUN(MI355_KC_GEMM_QUANT, mi355_linear_forward(b.xn, T, &L.qkv, L.qkv_bias, b.qkv, MI355_EPI_NONE, b.gemm_ws, b.gemm_ws_bytes, st));
-        RUN(MI355_KC_ROPE_KV, mi355_rope_kv_write_rows(b.qkv, nullptr, 0, L.qkv.N, nullptr, d->prefill_cos_sin ? d->prefill_cos_sin : d->model.cos_sin, c.rope_dim, c.max_pos, positions,
-                                                       block_table, c.max_blocks_per_seq, T, q_len, c.nh, &kv, b.q, d->oob_count, st));
+        const float* cs = d->prefill_cos_sin ? d->prefill_cos_sin : d->model.cos_sin;
+        if (!d->q_norm.empty())
+            RUN(MI355_KC_ROPE_KV, mi355_rope_kv_write_rows_qk_norm(b.qkv, nullptr, 0, L.qkv.N, nullptr, d->q_norm[l], d->k_norm[l], c.rms_eps, cs, c.rope_dim,
+                                                                   c.max_pos, positions, block_table, c.max_blocks_per_seq, T, q_len, c.nh, &kv, b.q,
+                                                                   d->oob_count, st));
+        else
+            RUN(MI355_KC_ROPE_KV, mi355_rope_kv_write_rows(b.qkv, nullptr, 0, L.qkv.N, nullptr, cs, c.rope_dim, c.max_pos, positions,
+                                                           block_table, c.max_blocks_per_seq, T, q_len, c.nh, &kv, b.q, d->oob_count, st));
         RUN(MI355_KC_ATTN, mi355_paged_attn_rows(b.q, &kv, block_table, c.max_blocks_per_seq, positions, nseq, q_len, c.nh, scale,
                                                  c.max_seq_len, b.attn, b.attn_ws, b.attn_ws_bytes, st));
         RUN(MI355_KC_GEMM_QUANT, mi355_linear_forward(b.attn, T, &L.o, nullptr, b.tmp, MI355_EPI_NONE, b.gemm_ws, b.gemm_ws_bytes, st));

@@ -10,6 +10,11 @@
 // One wave per (token, head): lane i owns the NeoX pair (i, i + hd/2)
 // (rotary_position_embedding.h:278-321,444-449: x' = cos*x - sin*y, y' = cos*y + sin*x
 // in fp32, one rounding to fp16).  Launch-bound by nature (T*(nh+2nkv) waves).
+//
+// Qwen3 form (QKN, mi355_rope_kv_write_rows_qk_norm): per-head RMSNorm of every Q and K head between the bias add and the
+// rotation -- the step the reference's fused_qk_rmsnorm_v2 runs as a launch of its own.  The wave already
+// holds the whole head, so the norm costs one wave_sum: y = w * act(x * rsqrt(sum(x^2) / hd + eps)), fp32 sum of squares,
+// w = q_norm / k_norm [hd] shared by all heads (HF Qwen3RMSNorm, the arithmetic of oracle.rmsnorm); V heads are untouched.
 #include "common.h"
 
 namespace {
@@ -28,10 +33,14 @@ struct RopeParams {
     float*         scale_base;
     int            kv_int8;
     f16*           q_out;
+    const f16*     q_norm;   // QKN only: [hd] weights of the per-head norms
+    const f16*     k_norm;
+    float          eps;
 };
 
 // BF: qkv / bias / q_out and a 16-bit cache are bf16 (kv_dtype MI355_KV_BF16); the INT8 cache is quantised from the same fp32 values either way
-template <bool BF>
+// QKN: per-head RMSNorm of Q and K before the rotation (Qwen3); false compiles to the Qwen2 / Llama writer
+template <bool BF, bool QKN>
 __global__ __launch_bounds__(256) void rope_kv_write_kernel(const RopeParams p) {
     using raw16 = uint16_t;
     const int t    = blockIdx.x;
@@ -53,6 +62,13 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(const RopeParams p) 
     const int blk = (h >= p.nh) ? p.block_table[(size_t)(t / p.q_len) * p.max_blocks + pos / p.page] : 0;
     float2 cs = {1.f, 0.f};
     if (!is_v && act) cs = *reinterpret_cast<const float2*>(p.cos_sin + ((size_t)pos * half + lane) * 2);
+    uint16_t nw0 = 0, nw1 = 0;   // QKN: this lane's pair of norm weights, requested with the rotation row
+    if constexpr (QKN) {
+        if (!is_v && act) {
+            const raw16* nw = reinterpret_cast<const raw16*>(h < p.nh ? p.q_norm : p.k_norm);
+            nw0 = nw[lane]; nw1 = nw[lane + half];
+        }
+    }
     float x0 = 0.f, x1 = 0.f;
     if (act) {
         float bh0 = 0.f, bh1 = 0.f;
@@ -80,6 +96,15 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(const RopeParams p) 
         x0 += bh0; x1 += bh1;
         // the QKV linear's output is a 16-bit tensor in the reference
         x0 = act_round<BF>(x0); x1 = act_round<BF>(x1);
+    }
+    if constexpr (QKN) {
+        if (!is_v) {   // wave-uniform: every lane takes part in the sum (lanes past hd/2 add zero)
+            const float ss = wave_sum(act ? x0 * x0 + x1 * x1 : 0.f);
+            const float rs = rsqrtf(ss / (float)p.hd + p.eps);
+            // weight * act(x * rs): the product of two 16-bit values is exact in fp32, so one rounding makes it the 16-bit product
+            x0 = act_round<BF>(act_from_bits<BF>(nw0) * act_round<BF>(x0 * rs));
+            x1 = act_round<BF>(act_from_bits<BF>(nw1) * act_round<BF>(x1 * rs));
+        }
     }
     if (!is_v && act) {
         const float r0 = cs.x * x0 - cs.y * x1;
@@ -138,11 +163,11 @@ extern "C" int mi355_rope_kv_write(const void* qkv_f16, const float* partials, i
                                     max_blocks_per_seq, T, 1, nh, kv, q_out, oob_count, stream);
 }
 
-extern "C" int mi355_rope_kv_write_rows(const void* qkv_f16, const float* partials, int32_t nsplit, int32_t ld,
-                                        const void* qkv_bias, const float* cos_sin, int32_t rope_dim, int32_t max_pos,
-                                        const int32_t* positions, const int32_t* block_table, int32_t max_blocks_per_seq,
-                                        int32_t T, int32_t q_len, int32_t nh, const mi355_kv_layer_t* kv, void* q_out,
-                                        int32_t* oob_count, mi355_stream_t stream) {
+namespace {
+int rope_kv_launch(const void* qkv_f16, const float* partials, int32_t nsplit, int32_t ld, const void* qkv_bias, const void* q_norm,
+                   const void* k_norm, float eps, const float* cos_sin, int32_t rope_dim, int32_t max_pos, const int32_t* positions,
+                   const int32_t* block_table, int32_t max_blocks_per_seq, int32_t T, int32_t q_len, int32_t nh, const mi355_kv_layer_t* kv,
+                   void* q_out, int32_t* oob_count, mi355_stream_t stream) {
     MI355_CHECK_ARG(q_len >= 1 && T % q_len == 0, "rope_kv_write: T=%d must be a multiple of q_len=%d", T, q_len);
     MI355_CHECK_ARG((qkv_f16 != nullptr) != (partials != nullptr), "rope_kv_write: exactly one of qkv_f16 / partials");
     MI355_CHECK_ARG(kv && kv->kv_base && cos_sin && positions && block_table && q_out, "rope_kv_write: null pointer");
@@ -157,16 +182,44 @@ extern "C" int mi355_rope_kv_write_rows(const void* qkv_f16, const float* partia
                     "rope_kv_write: act_dtype=%d with kv_dtype=%d (a 16-bit cache has the dtype of the activations)", kv->act_dtype, kv->kv_dtype);
     const int nheads = nh + 2 * kv->nkv;
     MI355_CHECK_ARG(ld >= nheads * kv->hd, "rope_kv_write: ld=%d", ld);
+    const bool qkn = q_norm != nullptr || k_norm != nullptr;
+    MI355_CHECK_ARG(!qkn || (q_norm && k_norm && eps >= 0.f), "rope_kv_write_qk_norm: needs both q_norm and k_norm and eps >= 0");
     RopeParams p;
     p.qkv = (const f16*)qkv_f16; p.partials = partials; p.nsplit = nsplit; p.ld = ld; p.bias = (const f16*)qkv_bias;
     p.cos_sin = cos_sin; p.positions = positions; p.block_table = block_table; p.max_blocks = max_blocks_per_seq;
     p.T = T; p.nh = nh; p.nkv = kv->nkv; p.hd = kv->hd; p.page = kv->page; p.kv_base = kv->kv_base;
     p.max_pos = max_pos; p.num_blocks = kv->num_blocks; p.oob_count = oob_count; p.q_len = q_len;
     p.scale_base = kv->scale_base; p.kv_int8 = kv->kv_dtype == MI355_KV_INT8; p.q_out = (f16*)q_out;
-    if (bf)
-        hipLaunchKernelGGL(rope_kv_write_kernel<true>, dim3(T, cdiv(nheads, 4)), dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(rope_kv_write_kernel<false>, dim3(T, cdiv(nheads, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    p.q_norm = (const f16*)q_norm; p.k_norm = (const f16*)k_norm; p.eps = eps;
+    const dim3 grid(T, cdiv(nheads, 4));
+    if (qkn) {
+        if (bf) hipLaunchKernelGGL((rope_kv_write_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else    hipLaunchKernelGGL((rope_kv_write_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    } else {
+        if (bf) hipLaunchKernelGGL((rope_kv_write_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else    hipLaunchKernelGGL((rope_kv_write_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    }
     MI355_CHECK_LAUNCH("rope_kv_write_kernel");
     return MI355_OK;
+}
+} // namespace
+
+extern "C" int mi355_rope_kv_write_rows(const void* qkv_f16, const float* partials, int32_t nsplit, int32_t ld,
+                                        const void* qkv_bias, const float* cos_sin, int32_t rope_dim, int32_t max_pos,
+                                        const int32_t* positions, const int32_t* block_table, int32_t max_blocks_per_seq,
+                                        int32_t T, int32_t q_len, int32_t nh, const mi355_kv_layer_t* kv, void* q_out,
+                                        int32_t* oob_count, mi355_stream_t stream) {
+    return rope_kv_launch(qkv_f16, partials, nsplit, ld, qkv_bias, nullptr, nullptr, 0.f, cos_sin, rope_dim, max_pos, positions, block_table,
+                          max_blocks_per_seq, T, q_len, nh, kv, q_out, oob_count, stream);
+}
+
+extern "C" int mi355_rope_kv_write_rows_qk_norm(const void* qkv_f16, const float* partials, int32_t nsplit, int32_t ld,
+                                                const void* qkv_bias, const void* q_norm, const void* k_norm, float eps,
+                                                const float* cos_sin, int32_t rope_dim, int32_t max_pos, const int32_t* positions,
+                                                const int32_t* block_table, int32_t max_blocks_per_seq, int32_t T, int32_t q_len,
+                                                int32_t nh, const mi355_kv_layer_t* kv, void* q_out, int32_t* oob_count,
+                                                mi355_stream_t stream) {
+    MI355_CHECK_ARG(q_norm && k_norm, "rope_kv_write_rows_qk_norm: q_norm and k_norm are required");
+    return rope_kv_launch(qkv_f16, partials, nsplit, ld, qkv_bias, q_norm, k_norm, eps, cos_sin, rope_dim, max_pos, positions, block_table,
+                          max_blocks_per_seq, T, q_len, nh, kv, q_out, oob_count, stream);
 }

@@ -59,12 +59,18 @@ class _Shards:
 def config_from_hf(cfg: dict, name: str = "hf-model") -> Tuple[ModelConfig, dict]:
     """config.json -> (ModelConfig, quantization dict) — the fields models/qwen_v2.py:338-399 reads."""
     nh = cfg["num_attention_heads"]
+    # newer transformers write RoPE settings as `rope_parameters` ({"rope_theta", "rope_type", ...}) instead of rope_theta / rope_scaling
+    rp = cfg.get("rope_parameters") or {}
+    theta = cfg.get("rope_theta", rp.get("rope_theta", 10000.0))
     mc = ModelConfig(name=name, num_layers=cfg["num_hidden_layers"], hidden=cfg["hidden_size"], nh=nh,
                      nkv=cfg.get("num_key_value_heads", nh), hd=cfg.get("head_dim", cfg["hidden_size"] // nh),
-                     inter=cfg["intermediate_size"], vocab=cfg["vocab_size"], rope_theta=float(cfg.get("rope_theta", 10000.0)),
+                     inter=cfg["intermediate_size"], vocab=cfg["vocab_size"], rope_theta=float(theta),
                      rms_eps=float(cfg.get("rms_norm_eps", 1e-6)), qkv_bias=False,
-                     max_pos=int(cfg.get("max_position_embeddings", 8192)))
-    rs = cfg.get("rope_scaling") or {}
+                     max_pos=int(cfg.get("max_position_embeddings", 8192)),
+                     qk_norm=cfg.get("model_type") == "qwen3")   # Qwen3 dense: per-head q_norm / k_norm (also set when the tensors are found)
+    if cfg.get("model_type") == "qwen3_moe":
+        raise NotImplementedError("mixture-of-experts models (Qwen3-MoE) are not on this decode path")
+    rs = cfg.get("rope_scaling") or {k: v for k, v in rp.items() if k != "rope_theta"}
     kind = rs.get("rope_type", rs.get("type", "default")) if rs else "default"
     if kind not in ("default", None):
         # linear / llama3 / yarn fold into the position-indexed cos/sin table (model.rope_frequencies); "dynamic" (models/llama.py:95-96,
@@ -122,7 +128,7 @@ def _linear_quant(sh: _Shards, prefix: str, method: str, group_size: int) -> Can
 def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 1, rank: int = 0,
                        max_layers: Optional[int] = None, split_embedding: bool = False,
                        dtype: torch.dtype = torch.float16) -> Tuple[ModelConfig, Dict]:
-    """Read an HF Qwen2/Llama checkpoint (fp16, GPTQ-4bit or AWQ-4bit) into the canonical weight dict of
+    """Read an HF Qwen2/Llama/Qwen3 checkpoint (fp16, GPTQ-4bit or AWQ-4bit) into the canonical weight dict of
     rtp_llm_amd.model (per-rank tensors when tp > 1).  quantization="int8" autoquantises fp16 linears at load time.
     split_embedding (tp > 1): the embedding table comes back as this rank's [vocab, hidden / tp] column slice, the reference's TP
     layout (utils/model_weight.py:1490 sp_neg1) -- pair it with DecoderEngine.set_embedding_split(); default: replicated table
@@ -152,6 +158,15 @@ def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 
 
     layers = []
     has_bias = False
+    # Qwen3: self_attn.{q,k}_norm.weight [hd] per layer.  Either every layer has both or the checkpoint is refused: a norm tensor the
+    # step would not apply must never be skipped silently (the logits would be wrong without an error)
+    qkn = [(sh.has(f"{pre}layers.{i}.self_attn.q_norm.weight"), sh.has(f"{pre}layers.{i}.self_attn.k_norm.weight")) for i in range(mc.num_layers)]
+    if any(a or b for a, b in qkn):
+        if not all(a and b for a, b in qkn):
+            raise ValueError("checkpoint has per-head q_norm / k_norm tensors on some layers only: not a model this decode path serves")
+        mc.qk_norm = True
+    elif mc.qk_norm:
+        raise ValueError("config.json says model_type 'qwen3' but the checkpoint has no self_attn.q_norm / k_norm tensors")
     for i in range(L):
         p = f"{pre}layers.{i}."
         qkv = CanonLinear.cat_cols([lin(p + "self_attn.q_proj"), lin(p + "self_attn.k_proj"), lin(p + "self_attn.v_proj")])
@@ -165,6 +180,12 @@ def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 
             "input_norm": _f16(sh.get(p + "input_layernorm.weight"), p + "input_layernorm", dtype),
             "post_norm": _f16(sh.get(p + "post_attention_layernorm.weight"), p + "post_attention_layernorm", dtype),
         }
+        if mc.qk_norm:
+            for k in ("q_norm", "k_norm"):
+                w = _f16(sh.get(p + f"self_attn.{k}.weight"), p + f"self_attn.{k}", dtype)
+                if w.shape != (mc.hd,):
+                    raise ValueError(f"{p}self_attn.{k}.weight: shape {tuple(w.shape)}, expected ({mc.hd},) (one weight per head channel)")
+                layer[k] = w
         layers.append(split_layer_tp(layer, mc, tp, rank))
     emb = _f16(sh.get(pre + "embed_tokens.weight"), "embed_tokens", dtype)
     if sh.has("lm_head.weight"):

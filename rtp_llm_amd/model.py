@@ -24,7 +24,7 @@ from .attention import AttentionConfigs, AttnImplFactory, LayerKVCache, PyAttent
 from .distributed import Group, all_gather, all_reduce
 from .kvcache import alloc_layer_cache
 from .linear import LinearFactory
-from .modules import Embedding, FusedSiluAndMul, RMSNorm
+from .modules import Embedding, FusedQKRMSNorm, FusedSiluAndMul, RMSNorm
 from .quant import PackedWeight
 
 
@@ -45,6 +45,9 @@ class ModelConfig:
     # scaled RoPE style, HF's `rope_scaling` dict ({"rope_type": "linear" | "llama3" | "yarn", "factor", ...}); None = base
     # (RopeStyle / RopeConfig, rtp_llm/cpp/model_utils/RopeConfig.h:7-40; mapping from config.json: models/llama.py:87-117)
     rope_scaling: Optional[dict] = None
+    # Qwen3 dense: per-head RMSNorm of Q and K (weights q_norm / k_norm [hd] per layer) between the QKV projection and RoPE
+    # (Qwen3Attention; the reference's FusedQKRMSNorm / fused_qk_rmsnorm_v2)
+    qk_norm: bool = False
 
     def per_rank(self, tp: int) -> "ModelConfig":
         """Per-rank attention/FFN dims (model_config.getAttentionConfigs(tp), qwen3.py:33;
@@ -80,7 +83,9 @@ QWEN2_7B = ModelConfig("qwen2-7b", 28, 3584, 28, 4, 128, 18944, 152064)
 QWEN2_0_5B = ModelConfig("qwen2-0.5b", 24, 896, 14, 2, 64, 4864, 151936)
 LLAMA3_70B = ModelConfig("llama3-70b", 80, 8192, 64, 8, 128, 28672, 128256, rope_theta=5e5, qkv_bias=False)
 QWEN2_72B = ModelConfig("qwen2-72b", 80, 8192, 64, 8, 128, 29568, 152064)
-MODELS = {m.name: m for m in (QWEN2_7B, QWEN2_0_5B, LLAMA3_70B, QWEN2_72B)}
+# Qwen3-8B config.json: head_dim 128 given explicitly, no QKV bias, per-head QK norm
+QWEN3_8B = ModelConfig("qwen3-8b", 36, 4096, 32, 8, 128, 12288, 151936, rope_theta=1e6, qkv_bias=False, qk_norm=True)
+MODELS = {m.name: m for m in (QWEN2_7B, QWEN2_0_5B, LLAMA3_70B, QWEN2_72B, QWEN3_8B)}
 
 
 # --------------------------------------------------------------------------- canonical weights
@@ -175,12 +180,16 @@ def synth_linear(K: int, N: int, kind: str, device, gen: torch.Generator, group_
 def synth_layer(cfg: ModelConfig, kind: str, device, gen, group_size=128, method="gptq", zeros="uniform") -> Dict:
     H, qkv_n = cfg.hidden, (cfg.nh + 2 * cfg.nkv) * cfg.hd
     lin = lambda K, N: synth_linear(K, N, kind, device, gen, group_size, method, zeros)
-    return {
+    layer = {
         "qkv": lin(H, qkv_n), "o": lin(cfg.nh * cfg.hd, H), "gate_up": lin(H, 2 * cfg.inter), "down": lin(cfg.inter, H),
         "qkv_bias": ((torch.rand(qkv_n, device=device, generator=gen) - 0.5) * 0.2).half() if cfg.qkv_bias else None,
         "input_norm": (1.0 + 0.1 * torch.randn(H, device=device, generator=gen)).half(),
         "post_norm": (1.0 + 0.1 * torch.randn(H, device=device, generator=gen)).half(),
     }
+    if cfg.qk_norm:   # drawn last: a config without the norms keeps its random stream
+        layer["q_norm"] = (1.0 + 0.2 * torch.randn(cfg.hd, device=device, generator=gen)).half()
+        layer["k_norm"] = (1.0 + 0.2 * torch.randn(cfg.hd, device=device, generator=gen)).half()
+    return layer
 
 
 def synth_model(cfg: ModelConfig, kind: str, device, seed: int = 0, group_size=128, method="gptq", zeros="uniform") -> Dict:
@@ -222,7 +231,7 @@ def split_embedding_tp(embedding: torch.Tensor, tp: int, rank: int) -> torch.Ten
 def split_layer_tp(layer: Dict, cfg: ModelConfig, tp: int, rank: int) -> Dict:
     """Megatron TP split of one layer (table utils/model_weight.py:1517-1563): column-parallel QKV
     (q heads / tp, k and v heads / tp) and gate/up, row-parallel O and down; norms replicated;
-    QKV bias split like the QKV columns."""
+    QKV bias split like the QKV columns; Qwen3's per-head q_norm / k_norm replicated (every rank's heads share them)."""
     if tp == 1:
         return layer
     hd, nh, nkv, I0 = cfg.hd, cfg.nh, cfg.nkv, cfg.inter
@@ -246,6 +255,9 @@ def split_layer_tp(layer: Dict, cfg: ModelConfig, tp: int, rank: int) -> Dict:
     if layer["qkv_bias"] is not None:
         b = layer["qkv_bias"]
         out["qkv_bias"] = torch.cat([b[q_lo:q_lo + nh_r * hd], b[k_lo:k_lo + nkv_r * hd], b[v_lo:v_lo + nkv_r * hd]]).contiguous()
+    for k in ("q_norm", "k_norm"):
+        if layer.get(k) is not None:
+            out[k] = layer[k]
     return out
 
 
@@ -336,15 +348,24 @@ def rope_table(cfg: ModelConfig, device) -> torch.Tensor:
 
 # --------------------------------------------------------------------------- Python module graph
 class CausalAttention(nn.Module):
-    """causal_attention.py:42-93: qkv_proj -> fmha_impl.forward -> o_proj -> all_reduce(TP)."""
+    """causal_attention.py:42-93: qkv_proj -> [Qwen3: FusedQKRMSNorm] -> fmha_impl.forward -> o_proj -> all_reduce(TP).
+    cfg: the (per-rank) config; needed when the layer carries q_norm / k_norm."""
 
-    def __init__(self, layer: Dict):
+    def __init__(self, layer: Dict, cfg: Optional[ModelConfig] = None):
         super().__init__()
         mk = lambda c, bias=None: LinearFactory.create_linear(c.w if c.kind == "fp16" else c.q, bias, c.scales, None, c.z_eff)
         self.qkv_proj, self.o_proj = mk(layer["qkv"], layer["qkv_bias"]), mk(layer["o"])
+        self.qk_norm = None
+        if layer.get("q_norm") is not None:
+            if cfg is None:
+                raise ValueError("CausalAttention: a layer with q_norm / k_norm needs the model config (heads, head size, eps)")
+            self.qk_norm = FusedQKRMSNorm(layer["q_norm"], layer["k_norm"], cfg.nh, cfg.nkv, cfg.hd, cfg.rms_eps)
 
     def forward(self, x, fmha_impl, kv_cache: LayerKVCache, layer_idx: int):
-        out = self.o_proj(fmha_impl.forward(self.qkv_proj(x), kv_cache, layer_idx))
+        qkv = self.qkv_proj(x)
+        if self.qk_norm is not None:
+            qkv = self.qk_norm(qkv)
+        out = self.o_proj(fmha_impl.forward(qkv, kv_cache, layer_idx))
         return all_reduce(out, Group.TP)
 
 
@@ -361,7 +382,8 @@ class DenseMLP(nn.Module):
 
 
 class Qwen2DecoderModel(nn.Module):
-    """qwen3.py:82-138 for the Qwen2/Llama family; forward(input_ids, attn_inputs, kv_caches) -> hidden."""
+    """qwen3.py:82-138 for the Qwen2/Llama family and Qwen3 dense (cfg.qk_norm: layers carry q_norm / k_norm);
+    forward(input_ids, attn_inputs, kv_caches) -> hidden."""
 
     def __init__(self, cfg: ModelConfig, weights: Dict, page: int, max_seq_len: int):
         super().__init__()
@@ -372,7 +394,7 @@ class Qwen2DecoderModel(nn.Module):
         for L in weights["layers"]:
             m = nn.Module()
             m.input_layernorm, m.post_attention_layernorm = RMSNorm(L["input_norm"], cfg.rms_eps), RMSNorm(L["post_norm"], cfg.rms_eps)
-            m.self_attn, m.mlp = CausalAttention(L), DenseMLP(L)
+            m.self_attn, m.mlp = CausalAttention(L, cfg), DenseMLP(L)
             self.layers.append(m)
         self.norm = RMSNorm(weights["final_norm"], cfg.rms_eps)
         self.lm_head = LinearFactory.create_linear(weights["lm_head"].w)
@@ -429,9 +451,17 @@ class DecoderEngine:
         self.packed_bytes = 0
         lw = (_C.LayerWeights * cfg.num_layers)()
         self.kv, self.kv_scale = [], []
+        has_qkn = [L.get("q_norm") is not None and L.get("k_norm") is not None for L in weights["layers"]]
+        if any(has_qkn) != bool(cfg.qk_norm) or not (all(has_qkn) or not any(has_qkn)):
+            raise ValueError(f"DecoderEngine: cfg.qk_norm={cfg.qk_norm} but q_norm / k_norm are present in {sum(has_qkn)} of {len(has_qkn)} layers")
+        qn_ptrs, kn_ptrs = (C.c_void_p * cfg.num_layers)(), (C.c_void_p * cfg.num_layers)()
         for i, L in enumerate(weights["layers"]):
             p = {k: L[k].pack(gate_up=(k == "gate_up"), dtype=dtype) for k in ("qkv", "o", "gate_up", "down")}
-            aux = {k: cast(L[k]) for k in ("qkv_bias", "input_norm", "post_norm")}
+            aux = {k: cast(L.get(k)) for k in ("qkv_bias", "input_norm", "post_norm", "q_norm", "k_norm")}
+            if cfg.qk_norm:
+                if aux["q_norm"].numel() != cfg.hd or aux["k_norm"].numel() != cfg.hd:
+                    raise ValueError(f"DecoderEngine: layer {i}: q_norm / k_norm must have hd={cfg.hd} elements")
+                qn_ptrs[i], kn_ptrs[i] = aux["q_norm"].data_ptr(), aux["k_norm"].data_ptr()
             self._keep.append((p, L, aux))
             self.packed_bytes += sum(v.nbytes for v in p.values())
             kvb, kvs = alloc_layer_cache(num_blocks, cfg.nkv, page, cfg.hd, kv_int8, device, dtype=dtype)
@@ -466,6 +496,8 @@ class DecoderEngine:
         self.handle = self.lib.mi355_decoder_create(C.byref(mc), lw, C.byref(mw), C.byref(sb))
         if not self.handle:
             raise _C.Mi355Error("decoder_create failed: " + self.lib.mi355_last_error().decode())
+        if cfg.qk_norm:   # Qwen3: before any step -- the QKV half of every layer becomes split-K + the normalising KV writer
+            _C.check(self.lib.mi355_decoder_set_qk_norm(self.handle, qn_ptrs, kn_ptrs), "decoder_set_qk_norm")
 
     def __del__(self):
         try:

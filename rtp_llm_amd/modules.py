@@ -1,6 +1,6 @@
 """Leaf modules with the reference's call shapes (rtp_llm/models_py/modules/base/__init__.py:26-60):
 RMSNorm(weight, eps)(x), RMSResNorm(weight, eps)(x, residual) -> (y, residual_out),
-FusedSiluAndMul()(gate_up), Embedding(weight)(ids).  Each forwards to one HIP kernel."""
+FusedQKRMSNorm(q_weight, k_weight, nh, nkv, hd, eps)(qkv), FusedSiluAndMul()(gate_up), Embedding(weight)(ids).  Each forwards to one HIP kernel."""
 import torch
 from torch import nn
 
@@ -27,6 +27,18 @@ class RMSResNorm(nn.Module):
 
     def forward(self, x: torch.Tensor, residual: torch.Tensor):
         return ops.add_rmsnorm(x.contiguous(), residual.contiguous(), self.weight, self.eps)
+
+
+class FusedQKRMSNorm(nn.Module):
+    """Qwen3's per-head Q / K RMSNorm on the packed qkv rows, ahead of the fmha op (the reference's FusedQKRMSNorm,
+    fused_qk_rmsnorm_v2) -> ops.qk_rmsnorm_, in place."""
+
+    def __init__(self, q_weight: torch.Tensor, k_weight: torch.Tensor, nh: int, nkv: int, hd: int, eps: float = 1e-6):
+        super().__init__()
+        self.q_weight, self.k_weight, self.nh, self.nkv, self.hd, self.eps = q_weight, k_weight, nh, nkv, hd, eps
+
+    def forward(self, qkv: torch.Tensor) -> torch.Tensor:
+        return ops.qk_rmsnorm_(qkv.contiguous(), self.q_weight, self.k_weight, self.eps, self.nh, self.nkv, self.hd)
 
 
 class FusedSiluAndMul(nn.Module):

@@ -410,6 +410,18 @@ def add_rmsnorm(x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, e
     return y, res_out
 
 
+def qk_rmsnorm_(qkv: torch.Tensor, q_norm: torch.Tensor, k_norm: torch.Tensor, eps: float, nh: int, nkv: int, hd: int) -> torch.Tensor:
+    """In place on packed QKV rows [T, (nh + 2 nkv) hd]: per-head RMSNorm of the Q heads with q_norm [hd], of the K heads with k_norm
+    (the reference's fused_qk_rmsnorm_v2 under FusedQKRMSNorm); V untouched.  Returns qkv."""
+    _chk_act(qkv, "qk_rmsnorm.qkv"); _chk_act(q_norm, "qk_rmsnorm.q_norm", qkv); _chk_act(k_norm, "qk_rmsnorm.k_norm", qkv)
+    if q_norm.numel() != hd or k_norm.numel() != hd or qkv.shape[-1] != (nh + 2 * nkv) * hd:
+        raise _C.Mi355Error(f"qk_rmsnorm: qkv width {qkv.shape[-1]} / norm sizes {q_norm.numel()}, {k_norm.numel()} do not fit nh={nh} nkv={nkv} hd={hd}")
+    T = qkv.numel() // qkv.shape[-1]
+    _C.check(_C.lib().mi355_qk_rmsnorm(qkv.data_ptr(), T, qkv.shape[-1], nh, nkv, hd, q_norm.data_ptr(), k_norm.data_ptr(), eps, _dt(qkv),
+                                       _stream()), "qk_rmsnorm")
+    return qkv
+
+
 def silu_mul(gate_up: torch.Tensor) -> torch.Tensor:
     _chk_act(gate_up, "silu_mul.gate_up")
     I = gate_up.shape[-1] // 2
@@ -593,6 +605,29 @@ def rope_kv_write_rows(qkv: torch.Tensor, qkv_bias, cos_sin, positions, block_ta
                                                cos_sin.shape[0], positions.data_ptr(), block_table.data_ptr(), block_table.shape[1],
                                                T, q_len, nh, C.byref(kv), q_out.data_ptr(), _p(oob_count), _stream()),
              "rope_kv_write_rows")
+    return q_out
+
+
+def rope_kv_write_rows_qk_norm(qkv: torch.Tensor, qkv_bias, q_norm: torch.Tensor, k_norm: torch.Tensor, eps: float, cos_sin, positions,
+                               block_table, kv_base, scale_base, nh: int, nkv: int, hd: int, page: int, q_len: int = 1,
+                               oob_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Qwen3 form of rope_kv_write_rows: per-head RMSNorm of every Q and K head (q_norm / k_norm [hd], shared by the heads) between the
+    bias add and the rotation, in the same launch."""
+    _chk_act(qkv, "rope_kv_write_rows_qk_norm.qkv"); _chk(positions, torch.int32, "positions"); _chk(block_table, torch.int32, "block_table")
+    _chk(cos_sin, torch.float32, "cos_sin")
+    _chk_act(q_norm, "q_norm", qkv); _chk_act(k_norm, "k_norm", qkv)
+    if q_norm.numel() != hd or k_norm.numel() != hd:
+        raise _C.Mi355Error(f"rope_kv_write_rows_qk_norm: q_norm / k_norm must have hd={hd} elements")
+    if qkv_bias is not None:
+        _chk(qkv_bias, qkv.dtype, "rope_kv_write_rows_qk_norm.qkv_bias")
+    T = qkv.shape[0]
+    q_out = torch.empty(T, nh, hd, dtype=qkv.dtype, device=qkv.device)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, qkv.dtype)
+    _C.check(_C.lib().mi355_rope_kv_write_rows_qk_norm(qkv.data_ptr(), None, 0, qkv.shape[1], _p(qkv_bias), q_norm.data_ptr(),
+                                                       k_norm.data_ptr(), eps, cos_sin.data_ptr(), hd, cos_sin.shape[0], positions.data_ptr(),
+                                                       block_table.data_ptr(), block_table.shape[1], T, q_len, nh, C.byref(kv),
+                                                       q_out.data_ptr(), _p(oob_count), _stream()),
+             "rope_kv_write_rows_qk_norm")
     return q_out
 
 
