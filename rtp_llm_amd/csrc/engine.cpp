@@ -8,17 +8,21 @@
 // (rtp_llm/cpp/models/PyWrappedModel.cc:938-1080, bindings/core/CudaSampleOp.cc:687-700)
 // and the per-batch-size graph capture of rtp_llm/cpp/cuda_graph/cuda_graph_runner.cc.
 //
-// Launches per layer (tp = 1):
-//   * 5-64 rows (bf16 and per-channel W8: 1-64), W4 group-wise or W8 per-channel weights, 16-bit cache (rounds 4-5): SIX launches, activations handed over as fragment-ordered images
-//     (common.h act_img_index): QKV + bias + RoPE + KV write (gemm_fullk64.hip) -> paged attention (+ partition reduce) ->
-//     O + residual, leaving gamma 2^-e h' as an image and the sums of squares -> gate_up + SiLU with the RMSNorm finished on its
-//     accumulators (gemm_wide.hip) -> down as 4 K-quarters (gemm_splitk64.hip) -> fold: slabs + residual + RMSNorm -> image;
-//   * up to 4 rows every GEMM is a full-K launch with its consumer fused (gemm_fullk.hip), 6 launches:
-//     [RMSNorm on load +] QKV + bias + RoPE + KV write -> attention -> partition reduce -> O + residual (leaves the
-//     per-tile sums of squares) -> RMSNorm on load + gate_up + SiLU-gate -> down + residual;
-//   * other formats / TP (above 12 rows): QKV GEMM (split-K slabs) -> reduce+bias+RoPE+KV-write -> paged attention (+ partition
-//     reduce) -> O GEMM (slabs) -> reduce+residual+RMSNorm -> gate_up GEMM with fused SiLU-gate -> down GEMM (slabs) ->
-//     reduce+residual+RMSNorm (already the next layer's input norm).  No standalone reduce / add / activation kernels.
+// Launch table.  Rows: configuration classes; columns: the stages of one layer; cells: the entry point (mi355_ dropped, " = as above).  plan_launches decides once
+// which classes the config and the weights allow (LaunchCaps), resolve_step picks one selector per stage for a step (StepPlan): a new launch variant is a new
+// cell here, a selector value there and one case in its stage's switch.  A published O or down shard falls back to its slab cell on its own (K too deep).
+//   class                                                 | QKV                                           | O                                   | gate_up                  | down                                | partial sums + residual + next norm
+//   tp 1, <= fuse_rows (W4, fp16 step: gemm_fullk.hip)    | qkv_rope_kv_write [norm on load from layer 1] | linear_residual [+ sums of squares] | norm_linear              | linear_residual [+ sums of squares] | in the epilogues (rmsnorm launch: no fused norm; the final norm)
+//   tp 1, > fuse_rows: images (fullk64 / wide / splitk64) | qkv_rope_kv_write_img                         | linear_residual_prenorm_img         | linear_deferred_norm_img | linear_partial_img (4 K quarters)   | add_rmsnorm_img_touch (final norm: add_rmsnorm)
+//     ... gate_up / down without their image launch       | "                                             | linear_residual_img + rmsnorm       | linear_direct            | linear_partial                      | "
+//     ... INT8 cache, Qwen3 QK norm                       | linear_partial + rope_kv_write_rows[_qk_norm] | "                                   | "                        | "                                   | add_rmsnorm
+//   other formats: staged split-K                         | linear_partial + rope_kv_write_rows           | linear_partial                      | linear_direct            | linear_partial                      | add_rmsnorm
+//   TP attached, > tp_fuse_rows, published                | qkv_rope_kv_write_img                         | linear_publish_img                  | linear_direct_img        | linear_publish_img                  | allreduce_fused_published
+//   TP attached, > tp_fuse_rows, slabs                    | qkv_rope_kv_write_img                         | linear_partial                      | linear_direct[_img]      | linear_partial_img                  | allreduce_fused_img
+//   TP attached, <= tp_fuse_rows                          | qkv_rope_kv_write, or as staged               | linear_partial                      | linear_direct            | linear_partial                      | allreduce_fused
+//   TP, external transport / segment caller               | "                                             | linear_partial                      | linear_direct            | linear_partial                      | add_rmsnorm (fold -> ar_buf) + all-reduce; add_rmsnorm opens the next segment
+// Between QKV and O: paged_attn_rows (+ partition reduce), as paged_attn_rows_img where the O launch reads an image.  Activations are handed over row-major
+// or as fragment-ordered images (common.h act_img_index); no standalone reduce / add / activation kernels.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <algorithm>
@@ -40,7 +44,33 @@ namespace {
 constexpr int kMaxSplits = 16;
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int    imax(int a, int b) { return a > b ? a : b; }
+inline int    ssq_pitch(const mi355_model_config_t& c) { return (c.hidden / 16 + 3) & ~3; }   // row pitch of the per-tile sums of squares: hidden / 16 rounded up to 4
+inline size_t weight_bytes(const mi355_weight_t* w) { return (size_t)w->K_pad * w->N_pad * w->wbits / 8; }
 } // namespace
+
+// What the config and the weight formats allow, decided once (plan_launches).  Each field is documented where it is computed.
+struct LaunchCaps {
+    bool fuse_qkv, fuse_o, fuse_down, fuse_norm;   // few-row full-K launches with their consumer fused (gemm_fullk.hip)
+    bool img_qkv, img_o, img_gate_up, img_down;    // tp = 1: launches on activation images (gemm_fullk64 / gemm_wide / gemm_splitk64.hip)
+    bool tp_img_qkv, tp_img_down, tp_img_gate;     // the same launches for the shards of a TP step with the all-reduce context attached
+    bool tp_pub_o, tp_pub_down;                    // row-parallel shards published straight into the registered all-reduce buffer
+    int  fuse_rows, tp_fuse_rows;                  // up to this many rows the (TP) step keeps the few-row launches
+};
+// The launch chain of ONE step: one selector per stage, resolved in mi355_decoder_begin_rows (resolve_step) and read by every launch
+// site.  Each activation hand-over has one layout flag, derived from its CONSUMER's selector; producer and consumer both read it.
+enum class QkvSel  { IMG, FULLK, SPLITK };
+enum class OSel    { PUBLISH, IMG_PRENORM, IMG, FULLK, SPLITK };
+enum class GateSel { DEFERRED_NORM_IMG, NORM_ON_LOAD, DIRECT_IMG, DIRECT };
+enum class DownSel { FULLK, PUBLISH, QUARTERS, SPLITK };
+enum class MeetSel { LOCAL, FUSED_AR, EXT };   // where partial sums, residual and norm meet: tp = 1 | attached context | local fold + external all-reduce
+struct StepPlan {
+    QkvSel qkv; OSel o; GateSel gate_up; DownSel down; MeetSel meet;
+    bool xn_is_image;        // normed hidden rows into QKV: xn_img, else xn
+    bool attn_is_image;      // attention output into O: attn_img, else attn_out
+    bool gate_in_is_image;   // (pre-)normed rows into gate_up: xg_img, else xn
+    bool act_is_image;       // SiLU-gated rows into down: act_img, else act
+    bool resid_ssq;          // no norm launches: O / down leave the per-tile sums of squares (ssq), QKV / gate_up normalise resid on load
+};
 
 struct mi355_decoder {
     mi355_model_config_t               cfg;
@@ -49,7 +79,9 @@ struct mi355_decoder {
     mi355_step_buffers_t               bufs;
     // carved workspace
     void *resid, *xn, *q_buf, *attn_out, *act, *attn_ws, *argmax_ws;
-    void *xn_img, *attn_img;   // activation images (mi355_act_image_*) of the normed hidden rows / the attention output, 5-64-row steps
+    // activation images (mi355_act_image_*), see StepPlan: the normed hidden rows, the attention output, gate_up's input (gamma 2^-e h' where
+    // the norm is deferred), the SiLU-gated rows
+    void *xn_img, *attn_img, *xg_img, *act_img;
     int32_t* oob_count; // tokens refused by the KV writer (stale position / block id)
     const float* prefill_cos_sin = nullptr;   // mi355_decoder_set_prefill_rope_table: {cos, sin} rows of the NEXT prefill chunks (dynamic-NTK prompts past the original context), or null
     mi355_allreduce_t* ar; // attached all-reduce context (tp_size > 1): the TP step runs entirely from C++
@@ -77,42 +109,13 @@ struct mi355_decoder {
     int32_t* iota;           // [max_batch] 0, 1, 2, ...: "logits of every row"
     int    B;       // rows of the step in flight (= sequences * q_len)
     int    q_len;   // rows per sequence: 1 = decode, > 1 = target-verify / prefill chunk (causal over the paged cache)
-    // fused full-K launches (gemm_fullk.hip), decided once from the weight formats: QKV + bias + RoPE + KV write in one
-    // launch (fp16 cache), O / down projection + residual add without split-K slabs (tp = 1: under TP the partial sums
-    // of the row-parallel linears meet in the all-reduce first).  Only up to fuse_rows rows: every block reads ALL
-    // activation rows of its K range from L2, which is free at a few rows and 2x slower than the staged split-K kernels
-    // at 64 (measured M = 64: qkv+rope 20.8 vs 9.0 + 4.9 us, o 18.6 vs 9.7 + slab fold; M = 1: 6.8 vs 7.3 + 3.1 us)
-    bool   fuse_qkv, fuse_o, fuse_down, fuse_norm;
-    int    fuse_rows;
-    // 1-64 rows (tp = 1): QKV + bias + RoPE + KV write and O + residual as one full-K launch each (gemm_fullk64.hip), their
-    // activations handed over as images by the producing launches (RMSNorm fold, attention): 7 launches per layer instead of 8 + no slabs
-    bool   img_qkv, img_o;
-    // tensor parallelism with the in-step all-reduce attached (round 5): the column-parallel QKV shard runs as the same image launch --
-    // the fused all-reduce behind down_proj (and the first norm of the step) write the image it reads; the row-parallel O / down shards
-    // keep their slab launches (their partial sums meet in the all-reduce launch either way)
-    bool   tp_img_qkv;
-    int    tp_fuse_rows;    // up to this many rows the TP step keeps the few-row QKV launch (row-major input)
-    // ... and the row-parallel down_proj shard as K quarters (gemm_splitk64.hip) from the image the gate_up shard's SiLU epilogue writes:
-    // 2-4 slabs into the fused all-reduce launch instead of up to 15
-    bool   tp_img_down;
-    // ... and the column-parallel gate_up shard as ONE launch from an image (gemm_splitk64.hip, direct form) instead of the staged split-K kernel + fold:
-    // the fused all-reduce behind the O shard then writes its normed rows as that image (into xg_img: unused under TP otherwise)
-    bool   tp_img_gate;
-    // round 6: the row-parallel O / down shards as ONE full-K launch each whose epilogue writes the rank's rows straight into the registered all-reduce
-    // buffer (mi355_linear_publish_img), consumed by mi355_allreduce_fused_published_dt: no slabs, no fold + publish stage in front of the flag exchange
-    bool   tp_pub_o, tp_pub_down;
-    // ... and the post-attention RMSNorm deferred into gate_up's accumulators (mi355_deferred_norm_t): the O launch leaves
-    // gamma 2^-e h' as an image + the per-tile sums of h'^2, the wide GEMM applies rsqrt(mean h'^2 + eps) 2^e: 6 launches per layer
-    bool   img_gate_up;
-    // ... and down_proj as 4 K-quarters from the image gate_up's SiLU epilogue writes (gemm_splitk64.hip) instead of 15 slabs
-    bool   img_down;
-    void*  act_img;
-    std::vector<int> post_norm_exp;   // per layer: e >= log2(max |post_norm weight|)
-    void*  xg_img;                    // image of gamma 2^-e h'
-    float* ssq64;                     // [64][hidden / 16 rounded up to 4]
-    float* ssq;      // [16 rows][hidden / 16]: the producer GEMM's per-tile sums of h^2, consumed by the next GEMM's on-the-fly RMSNorm
+    LaunchCaps caps;   // plan_launches
+    StepPlan   plan;   // of the step in flight, like B and q_len
+    std::vector<int> post_norm_exp;   // per layer: e >= log2(max |post_norm weight|) of the deferred norm
+    // per-tile sums of h^2 a producer GEMM leaves for the next GEMM's on-the-fly RMSNorm, [rows][ssq_pitch]: 16 rows (few-row launches), 64 (images)
+    float *ssq, *ssq64;
     // Qwen3 (mi355_decoder_set_qk_norm): per-layer [hd] weights of the per-head Q / K RMSNorm, empty for Qwen2 / Llama.  Set, the QKV
-    // half of every layer is split-K + mi355_rope_kv_write_rows_qk_norm: the fused QKV launches (fuse_qkv, img_qkv, tp_img_qkv) are off
+    // half of every layer is split-K + mi355_rope_kv_write_rows_qk_norm: plan_launches takes the fused QKV launches away
     std::vector<const void*> q_norm, k_norm;
     bool   started;   // a step, prefill or capture has been enqueued: the launch plan is fixed
     // graphs
@@ -158,11 +161,11 @@ size_t carve_all(mi355_decoder* d, const mi355_model_config_t& c, void* base) {
     const size_t gw = (size_t)c.max_batch * 64 * 8;
     void* argmax_ws = cv.take(gw);
     void* oob = cv.take(256);
-    void* ssq = cv.take((size_t)16 * ((c.hidden / 16 + 3) & ~3) * 4);   // per-tile sums of squares of the residual rows (fused norm, <= 16 rows)
+    void* ssq = cv.take((size_t)16 * ssq_pitch(c) * 4);   // per-tile sums of squares of the residual rows (fused norm, <= 16 rows)
     void* xn_img = cv.take(mi355_act_image_bytes(64, c.hidden));
     void* xg_img = cv.take(mi355_act_image_bytes(64, c.hidden));
     void* act_img = cv.take(mi355_act_image_bytes(64, c.inter));
-    void* ssq64 = cv.take((size_t)64 * ((c.hidden / 16 + 3) & ~3) * 4);
+    void* ssq64 = cv.take((size_t)64 * ssq_pitch(c) * 4);
     void* attn_img = cv.take(mi355_act_image_bytes(64, qdim));
     const size_t wide_bytes = c.max_batch > 64 ? carve_prefill(c, c.max_batch, c.max_batch, nullptr, nullptr) : 0;
     void* wide_ws = cv.take(wide_bytes);
@@ -216,80 +219,88 @@ extern "C" size_t mi355_decoder_workspace_bytes(const mi355_model_config_t* cfg)
 }
 
 namespace {
-// Which launches serve which step heights, decided from the config and the weight formats (mi355_decoder_create) and again when
-// mi355_decoder_set_qk_norm takes the fused QKV launches away; the flags that depend on those (fuse_norm, fuse_rows, tp_fuse_rows,
-// tp_pub_o) follow.  The result is the mix an INT8-KV config runs: composed QKV reading xn, image O / gate_up / down at 5-64 rows.
+// Which launches serve which step heights (LaunchCaps), decided from the config and the weight formats in mi355_decoder_create and again
+// when mi355_decoder_set_qk_norm takes the fused QKV launches away.  The result is the mix an INT8-KV config runs: composed QKV reading
+// xn, image O / gate_up / down above fuse_rows.
 int plan_launches(mi355_decoder* d) {
     const mi355_model_config_t& c = d->cfg;
-    const bool bf_act = c.act_dtype == MI355_ACT_BF16;
-    // QKV + RoPE + KV write in one launch: a 16-bit cache of the activation dtype (INT8 caches keep the quantising writer of rope_kv.hip)
-    // (not with the per-head QK norm of Qwen3: a fused QKV launch's block / epilogue job owns 32 of a head's hd columns, the norm needs the whole head)
-    const bool qkn = !d->q_norm.empty();
-    d->fuse_qkv = c.kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && c.rope_dim == c.hd && !qkn;
-    d->fuse_o = d->fuse_down = c.tp_size == 1;
-    // crossover between the few-row full-K launches (gemm_fullk.hip, dense activation loads) and the launches on activation images
-    // (round 4, same box: b = 4 1.94 vs 2.05 ms, b = 5 2.16 vs 2.05, b = 8 2.28 vs 2.07, b = 12 2.64 vs 2.10; profiles/r04_batch_sweep_crossover.txt);
-    // without the image path (other weight formats, bf16, TP) the round-3 crossover to the staged kernels stays
-    d->fuse_rows = 12;
-   // tuning build: crossover experiments (tools/batch_sweep.py --tune 6=N)
-    // W4 layers only: for small fp16 models (the 0.5B draft of speculative decoding: 36-56 blocks per launch) the fused
-    // launches measured behind the staged kernels (draft step 1.11 vs 1.05 ms), although the kernels take fp16 weights
+    LaunchCaps& k = d->caps;
+    const bool bf_act = c.act_dtype == MI355_ACT_BF16, tp = c.tp_size > 1;
+    // QKV + bias + RoPE + KV write in one launch: a 16-bit cache of the activation dtype (INT8 caches keep the quantising writer of rope_kv.hip),
+    // not with the per-head QK norm of Qwen3 (a fused QKV launch's block / epilogue job owns 32 of a head's hd columns, the norm needs the whole head)
+    const bool qkv_fusable = c.kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && c.rope_dim == c.hd && d->q_norm.empty();
+    // few-row full-K launches (gemm_fullk.hip): QKV as above, O / down projection + residual add without split-K slabs (tp = 1: under TP the partial
+    // sums of the row-parallel linears meet in the all-reduce first).  Only up to fuse_rows rows: every block reads ALL activation rows of its K range
+    // from L2, which is free at a few rows and 2x slower than the staged split-K kernels at 64 (measured M = 64: qkv+rope 20.8 vs 9.0 + 4.9 us,
+    // o 18.6 vs 9.7 + slab fold; M = 1: 6.8 vs 7.3 + 3.1 us).  W4 layers only: for small fp16 models (the 0.5B draft of speculative decoding: 36-56
+    // blocks per launch) the fused launches measured behind the staged kernels (draft step 1.11 vs 1.05 ms), although the kernels take fp16 weights
     auto w4ok = [](const mi355_weight_t* w) { return w->wbits == 4 && mi355_fullk_weight_ok(w); };
+    k.fuse_qkv = qkv_fusable; k.fuse_o = k.fuse_down = !tp;
+    // the norm launches disappear as well when every GEMM of the few-row layer is a full-K launch: O / down leave the per-tile sums of squares of
+    // the new residual rows, QKV / gate_up rebuild 1 / rms from them and normalise on load
+    bool gate_w4 = c.hidden % 64 == 0;
     for (const auto& L : d->layers) {
-        d->fuse_qkv = d->fuse_qkv && w4ok(&L.qkv);
-        d->fuse_o = d->fuse_o && w4ok(&L.o);
-        d->fuse_down = d->fuse_down && w4ok(&L.down);
+        k.fuse_qkv = k.fuse_qkv && w4ok(&L.qkv); k.fuse_o = k.fuse_o && w4ok(&L.o); k.fuse_down = k.fuse_down && w4ok(&L.down);
+        gate_w4 = gate_w4 && w4ok(&L.gate_up);
     }
-    // the norm launches disappear as well when every GEMM of the small-batch layer is a full-K launch: O / down leave the
-    // per-tile sums of squares of the new residual rows, QKV / gate_up rebuild 1 / rms from them and normalise on load
-    d->fuse_norm = d->fuse_qkv && d->fuse_o && d->fuse_down && c.hidden % 64 == 0;
-    for (const auto& L : d->layers) d->fuse_norm = d->fuse_norm && w4ok(&L.gate_up);
-    // the 17-64-row full-K launches: W4 group-wise, K <= 5760 (gemm_fullk64.hip), single rank
-    // (either activation dtype: the images are fp16, the epilogues store the step's dtype -- the few-row launches above are fp16 only,
-    // mi355_fullk_weight_ok)
-    auto w64ok = [&](const mi355_weight_t* w) { return mi355_fullk64_weight_ok(w) != 0; };   // the launchers' own predicate (gemm.hip)
-    d->img_qkv = c.kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && c.rope_dim == c.hd && c.tp_size == 1 && !qkn;
-    d->img_o = c.tp_size == 1;
-    for (const auto& L : d->layers) { d->img_qkv = d->img_qkv && w64ok(&L.qkv); d->img_o = d->img_o && w64ok(&L.o); }
-    d->tp_img_qkv = c.tp_size > 1 && c.kv_dtype == (bf_act ? MI355_KV_BF16 : MI355_KV_FP16) && c.rope_dim == c.hd && c.hidden % 32 == 0 && !qkn &&
-                    c.max_batch >= 1 && TUNE(5) != 2;
-    for (const auto& L : d->layers) d->tp_img_qkv = d->tp_img_qkv && mi355_fullk64_qkv_ok(&L.qkv, c.hd) != 0;
-    d->tp_img_down = c.tp_size > 1 && c.inter % 32 == 0 && TUNE(5) != 4 && TUNE(5) != 2;
-    for (const auto& L : d->layers)
-        d->tp_img_down = d->tp_img_down && L.down.K % 128 == 0 && L.down.K_pad == L.down.K && L.down.K == c.inter && L.gate_up.N == 2 * c.inter &&
-                         mi355_gemm_splitk64_plan(64, L.down.N_pad / 16, L.down.K_pad / 128, L.down.wbits, L.down.group_size, kMaxSplits, nullptr) > 0;
-    d->tp_img_gate = d->tp_img_down && c.hidden % 32 == 0 && TUNE(5) != 3;
-    for (const auto& L : d->layers)
-        d->tp_img_gate = d->tp_img_gate && L.gate_up.K % 128 == 0 && L.gate_up.K_pad == L.gate_up.K &&
-                         mi355_gemm_splitk64_direct_plan(64, L.gate_up.N_pad / 16, L.gate_up.K_pad / 128, L.gate_up.wbits, L.gate_up.group_size) > 0;
-    d->tp_pub_o = d->tp_img_qkv && !(TUNE(8) & 1);
-    d->tp_pub_down = d->tp_img_down && !(TUNE(8) & 2);
-    for (const auto& L : d->layers) {
-        d->tp_pub_o = d->tp_pub_o && mi355_fullk64_publish_ok(&L.o) != 0;
-        // down: where K stays inside two or three chunks per wave (K <= 5760: tp 4 of Qwen2-7B, tp 8 of the 70B models); deeper shards keep the K quarters
-        d->tp_pub_down = d->tp_pub_down && mi355_fullk64_publish_ok(&L.down) != 0 && (L.down.K_pad / 128 <= 45 || (TUNE(8) & 4));
+    k.fuse_norm = k.fuse_qkv && k.fuse_o && k.fuse_down && gate_w4;
+    // tp = 1, 1-64 rows: QKV + bias + RoPE + KV write and O + residual as one full-K launch each on activation images handed over by the producing
+    // launches (gemm_fullk64.hip: W4 group-wise or per-channel W8, K <= 5760; either activation dtype: the images are fp16, the epilogues store the
+    // step's dtype).  TUNE(5) == 2: A/B against the split-K + fold launches
+    k.img_qkv = qkv_fusable && !tp && TUNE(5) != 2;
+    k.img_o = !tp && TUNE(5) != 2;
+    for (const auto& L : d->layers) {   // the launchers' own predicate (gemm.hip)
+        k.img_qkv = k.img_qkv && mi355_fullk64_weight_ok(&L.qkv) != 0; k.img_o = k.img_o && mi355_fullk64_weight_ok(&L.o) != 0;
     }
-    // from how many rows the TP step takes the image launches: with the down shard as K quarters they win from ONE row (one rank of tp 2,
-    // b = 1 / 2 / 4: 1.67 / 1.68 / 1.72 ms against 1.75 / 1.77 / 1.82 with the few-row QKV launch + 15 staged slabs; profiles/r05_tp_small_batch_crossover.txt);
-    // without that plan the few-row QKV launch keeps its rows (the tp = 1 crossover)
-    d->tp_fuse_rows = (bf_act || !d->fuse_qkv || d->tp_img_down) ? 0 : 4;
-    if (TUNE(6) > 0) d->tp_fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: crossover experiments
-    if (TUNE(5) == 2) d->img_qkv = d->img_o = false;   // tuning build: A/B against the split-K + fold launches
-    // bf16 / W8: no few-row full-K launches to cross over to (gemm_fullk.hip takes fp16 steps of W4 / fp16 weights; the staged kernels lose
-    // at every height): the image launches serve 1-64 rows
-    if (d->img_qkv && d->img_o) d->fuse_rows = (bf_act || !(d->fuse_qkv && d->fuse_o && d->fuse_down)) ? 0 : 4;
-    if (TUNE(6) > 0) d->fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: crossover experiments (tools/batch_sweep.py --tune 6=N)
-    d->img_gate_up = d->img_o && c.hidden % 64 == 0 && TUNE(5) != 3;
-    for (const auto& L : d->layers) d->img_gate_up = d->img_gate_up && mi355_gemm_wide_direct_ok(&L.gate_up);
-    d->img_down = d->img_gate_up && c.inter % 32 == 0 && TUNE(5) != 4;
-    for (const auto& L : d->layers)
-        d->img_down = d->img_down && L.down.K % 128 == 0 && L.down.K_pad == L.down.K &&
-                      mi355_gemm_splitk64_plan(64, L.down.N_pad / 16, L.down.K_pad / 128, L.down.wbits, L.down.group_size, kMaxSplits, nullptr) > 0;
+    // ... the post-attention RMSNorm deferred into gate_up's accumulators (mi355_deferred_norm_t): the O launch leaves gamma 2^-e h' as an image + the
+    // per-tile sums of h'^2, the wide GEMM applies rsqrt(mean h'^2 + eps) 2^e: 6 launches per layer
+    k.img_gate_up = k.img_o && c.hidden % 64 == 0 && TUNE(5) != 3;
+    for (const auto& L : d->layers) k.img_gate_up = k.img_gate_up && mi355_gemm_wide_direct_ok(&L.gate_up);
+    // ... and down_proj as 4 K-quarters from the image gate_up's SiLU epilogue writes (gemm_splitk64.hip) instead of 15 slabs
+    auto quarters_ok = [](const mi355_weight_t& w) {
+        return w.K % 128 == 0 && w.K_pad == w.K && mi355_gemm_splitk64_plan(64, w.N_pad / 16, w.K_pad / 128, w.wbits, w.group_size, kMaxSplits, nullptr) > 0;
+    };
+    k.img_down = k.img_gate_up && c.inter % 32 == 0 && TUNE(5) != 4;
+    for (const auto& L : d->layers) k.img_down = k.img_down && quarters_ok(L.down);
     // bf16: the wide GEMM's image entry only exists with an image OUTPUT (gemm.hip mi355_linear_deferred_norm_img): without the
     // K-quarter down launch that reads it, gate_up goes back to norm launch + staged kernel instead of failing every step
-    if (bf_act && !d->img_down) d->img_gate_up = false;
+    if (bf_act && !k.img_down) k.img_gate_up = false;
+    // tensor parallelism with the in-step all-reduce attached: the column-parallel QKV shard runs as the same image launch -- the fused all-reduce
+    // behind down_proj (and the first norm of the step) write the image it reads
+    k.tp_img_qkv = tp && qkv_fusable && c.hidden % 32 == 0 && c.max_batch >= 1 && TUNE(5) != 2;
+    for (const auto& L : d->layers) k.tp_img_qkv = k.tp_img_qkv && mi355_fullk64_qkv_ok(&L.qkv, c.hd) != 0;
+    // ... the row-parallel down_proj shard as K quarters from the image the gate_up shard's SiLU epilogue writes: 2-4 slabs into the fused all-reduce
+    // launch instead of up to 15
+    k.tp_img_down = tp && c.inter % 32 == 0 && TUNE(5) != 4 && TUNE(5) != 2;
+    for (const auto& L : d->layers) k.tp_img_down = k.tp_img_down && quarters_ok(L.down) && L.down.K == c.inter && L.gate_up.N == 2 * c.inter;
+    // ... and the column-parallel gate_up shard as ONE launch from an image (gemm_splitk64.hip, direct form) instead of the staged split-K kernel +
+    // fold: the fused all-reduce behind the O shard then writes its normed rows as that image (into xg_img: unused under TP otherwise)
+    k.tp_img_gate = k.tp_img_down && c.hidden % 32 == 0 && TUNE(5) != 3;
+    for (const auto& L : d->layers)
+        k.tp_img_gate = k.tp_img_gate && L.gate_up.K % 128 == 0 && L.gate_up.K_pad == L.gate_up.K &&
+                        mi355_gemm_splitk64_direct_plan(64, L.gate_up.N_pad / 16, L.gate_up.K_pad / 128, L.gate_up.wbits, L.gate_up.group_size) > 0;
+    // the row-parallel O / down shards as ONE full-K launch each whose epilogue writes the rank's rows straight into the registered all-reduce buffer
+    // (mi355_linear_publish_img), consumed by mi355_allreduce_fused_published_dt: no slabs, no fold + publish stage in front of the flag exchange
+    k.tp_pub_o = k.tp_img_qkv && !(TUNE(8) & 1);
+    k.tp_pub_down = k.tp_img_down && !(TUNE(8) & 2);
+    for (const auto& L : d->layers) {
+        k.tp_pub_o = k.tp_pub_o && mi355_fullk64_publish_ok(&L.o) != 0;
+        // down: where K stays inside two or three chunks per wave (K <= 5760: tp 4 of Qwen2-7B, tp 8 of the 70B models); deeper shards keep the K quarters
+        k.tp_pub_down = k.tp_pub_down && mi355_fullk64_publish_ok(&L.down) != 0 && (L.down.K_pad / 128 <= 45 || (TUNE(8) & 4));
+    }
+    // fuse_rows: crossover between the few-row full-K launches (dense activation loads) and the launches on activation images (same box: b = 4 1.94 vs
+    // 2.05 ms, b = 5 2.16 vs 2.05, b = 8 2.28 vs 2.07, b = 12 2.64 vs 2.10; profiles/r04_batch_sweep_crossover.txt).  bf16 / W8 have no few-row launches
+    // to cross over to (gemm_fullk.hip takes fp16 steps of W4 / fp16 weights; the staged kernels lose at every height): the image launches serve 1-64
+    // rows.  Without the image path (other weight formats, TP) the earlier crossover to the staged kernels stays: 12
+    k.fuse_rows = !(k.img_qkv && k.img_o) ? 12 : (bf_act || !(k.fuse_qkv && k.fuse_o && k.fuse_down)) ? 0 : 4;
+    if (TUNE(6) > 0) k.fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: crossover experiments (tools/batch_sweep.py --tune 6=N)
+    // tp_fuse_rows: from how many rows the TP step takes the image launches.  With the down shard as K quarters they win from ONE row (one rank of tp 2,
+    // b = 1 / 2 / 4: 1.67 / 1.68 / 1.72 ms against 1.75 / 1.77 / 1.82 with the few-row QKV launch + 15 staged slabs;
+    // profiles/r05_tp_small_batch_crossover.txt); without that plan the few-row QKV launch (row-major input) keeps its rows (the tp = 1 crossover)
+    k.tp_fuse_rows = (bf_act || !k.fuse_qkv || k.tp_img_down) ? 0 : 4;
+    if (TUNE(6) > 0) k.tp_fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: the same switch
     d->post_norm_exp.clear();
-    if (d->img_gate_up) {   // exponent of the deferred norm per layer: the largest |weight| of post_norm, read back once
+    if (k.img_gate_up) {   // exponent of the deferred norm per layer: the largest |weight| of post_norm, read back once
         std::vector<uint16_t> g(c.hidden);
         for (const auto& L : d->layers) {
             if (hipMemcpy(g.data(), L.post_norm, (size_t)c.hidden * 2, hipMemcpyDeviceToHost) != hipSuccess) {
@@ -307,7 +318,7 @@ int plan_launches(mi355_decoder* d) {
             }
             int ex = 0;
             while (ex < 14 && ldexpf(1.f, ex) < mx) ++ex;
-            if (!(mx < INFINITY) || ldexpf(1.f, ex) < mx) { d->img_gate_up = false; break; }   // inf / nan / beyond 2^14 in a norm weight: keep the norm launch
+            if (!(mx < INFINITY) || ldexpf(1.f, ex) < mx) { k.img_gate_up = false; break; }   // inf / nan / beyond 2^14 in a norm weight: keep the norm launch
             // a bf16 residual stream may exceed the fp16 range of the image: eight more binary orders of headroom (|h| < 1.6e7), paid for with
             // precision only on elements below 2^-6 of a typical one
             d->post_norm_exp.push_back(bf_act ? (ex + 8 > 14 ? 14 : ex + 8) : ex);
@@ -377,9 +388,162 @@ extern "C" mi355_decoder_t* mi355_decoder_create(const mi355_model_config_t* cfg
     return d;
 }
 
+namespace {
+void drop_graphs(mi355_decoder* d) {   // captured steps bake the launch chain, the embedding path and the fork / join edges in
+    for (auto& kv : d->graphs) hipGraphExecDestroy(kv.second);
+    d->graphs.clear();
+}
+// the side stream and its two events: created once, ahead of any capture (not lazily inside one)
+bool side_ready(mi355_decoder* d) {
+    if (d->side_stream) return d->ev_fork && d->ev_join;
+    const bool ok = hipStreamCreateWithFlags(&d->side_stream, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming) == hipSuccess;
+    (void)hipGetLastError();
+    return ok;
+}
+// in-place sum of `count` 16-bit values over the TP ranks through the attached transport (no-op without one: the segment caller
+// all-reduces ar_buf itself between the calls)
+int ext_all_reduce(mi355_decoder* d, void* buf, size_t count, hipStream_t st) {
+    if (!d->has_ext) return MI355_OK;
+    const int rc = (d->cfg.act_dtype == MI355_ACT_BF16 ? d->ext.all_reduce_bf16 : d->ext.all_reduce_f16)(d->ext.ctx, buf, count, (mi355_stream_t)st);
+    if (rc != 0) { mi355_set_error("decoder: the attached transport's all-reduce failed (%d)", rc); return MI355_ERR_HIP; }
+    return MI355_OK;
+}
+
+constexpr size_t kPfCap = (size_t)48 << 20;          // bytes of one linear a side-stream prefetch pulls at most
+constexpr size_t kPfInLaunchCap = (size_t)8 << 20;   // MI355_PF_TP_INLAUNCH: bytes of the next shard one all-reduce launch requests (the
+                                                     // peer reads of its reduction queue behind them: vmcnt returns in order)
+// fork: from this point of `st` on, the side stream pulls up to kPfCap bytes of w into the Infinity Cache (plain event edges, so the
+// pair is captured into the step graph like everything else)
+int pf_fork(mi355_decoder* d, hipStream_t st, const mi355_weight_t* w) {
+    if (hipEventRecord(d->ev_fork, st) != hipSuccess || hipStreamWaitEvent(d->side_stream, d->ev_fork, 0) != hipSuccess) {
+        mi355_set_error("decoder: fork to the prefetch stream failed: %s", hipGetErrorString(hipGetLastError())); return MI355_ERR_HIP;
+    }
+    // the last dword of the oob block is never read by anyone: a harmless sink
+    return mi355_prefetch(w->qweight, std::min(weight_bytes(w), kPfCap), d->oob_count + 32, d->side_stream);
+}
+// all-reduce on `st`, prefetch of the next GEMM's weights on the side stream, joined before the GEMM
+template <class F>
+int comm_with_prefetch(mi355_decoder* d, hipStream_t st, const mi355_weight_t* next_w, F&& comm) {
+    const bool ov = d->overlap && (d->pf_mask & MI355_PF_TP_COMM) && next_w && next_w->qweight;
+    if ((d->pf_mask & MI355_PF_TP_INLAUNCH) && d->ar && next_w && next_w->qweight) {
+        // no second stream: the waves of the fused all-reduce launch that only wait for the peers' flags request the shard
+        const int rc = mi355_allreduce_set_prefetch(d->ar, next_w->qweight, std::min(weight_bytes(next_w), kPfInLaunchCap));
+        if (rc < 0) return rc;
+    }
+    if (ov) { const int rc = pf_fork(d, st, next_w); if (rc < 0) return rc; }
+    const int rc = comm();
+    if (rc < 0) return rc;
+    if (ov && (hipEventRecord(d->ev_join, d->side_stream) != hipSuccess || hipStreamWaitEvent(st, d->ev_join, 0) != hipSuccess)) {
+        mi355_set_error("decoder: join of the side stream failed: %s", hipGetErrorString(hipGetLastError())); return MI355_ERR_HIP;
+    }
+    return rc;
+}
+// tp = 1, weight prefetch one launch ahead: fork now, join (pf_join) in front of the linear that reads w
+int pf_issue(mi355_decoder* d, hipStream_t st, const mi355_weight_t* w) {
+    if (!w || !w->qweight || d->pf_pending || !side_ready(d)) return MI355_OK;
+    const int rc = pf_fork(d, st, w);
+    if (rc < 0) return rc;
+    if (hipEventRecord(d->ev_join, d->side_stream) != hipSuccess) {
+        mi355_set_error("decoder: prefetch stream event failed: %s", hipGetErrorString(hipGetLastError())); return MI355_ERR_HIP;
+    }
+    d->pf_pending = true;
+    return MI355_OK;
+}
+// join: launches issued on `st` after this point wait for the prefetch in flight (it has normally long finished)
+int pf_join(mi355_decoder* d, hipStream_t st) {
+    if (!d->pf_pending) return MI355_OK;
+    d->pf_pending = false;
+    if (hipStreamWaitEvent(st, d->ev_join, 0) != hipSuccess) {
+        mi355_set_error("decoder: join of the prefetch stream failed: %s", hipGetErrorString(hipGetLastError())); return MI355_ERR_HIP;
+    }
+    return MI355_OK;
+}
+#define PF_ISSUE(bits, w) do { if (pf & (bits)) if (int e__ = pf_issue(d, st, (w))) return e__; } while (0)
+
+// does the attached context take published rows for a B-row call right now?  Host state of the context only (ready, not on the
+// granule protocol, sizes): no caller changes that between begin and finish of a step, so one query per step
+bool pub_ready(const mi355_decoder* d, int B) {
+    mi355_publish_target_t t;
+    return d->ar && mi355_allreduce_publish_target(d->ar, B, d->cfg.hidden, &t) == MI355_OK;
+}
+
+// The launch chain of a B-row step: the row of the table at the top of this file.  Consumers first; every layout flag follows from
+// its consumer's selector and from nothing else.
+int resolve_step(mi355_decoder* d, int B) {
+    const LaunchCaps& k = d->caps;
+    StepPlan p;
+    p.meet = d->cfg.tp_size == 1 ? MeetSel::LOCAL : d->ar ? MeetSel::FUSED_AR : MeetSel::EXT;
+    const bool tp_mid = p.meet == MeetSel::FUSED_AR && B > k.tp_fuse_rows;   // TP step on the image launches (tp_img_* are tp > 1 only)
+    const bool mid = B > k.fuse_rows;                                        // tp = 1 step on the image launches (img_* are tp = 1 only)
+    const bool few = !(k.tp_img_qkv && tp_mid) && !mid;                      // the few-row full-K launches keep their rows
+    const bool pub = tp_mid && (k.tp_pub_o || k.tp_pub_down) && pub_ready(d, B);
+    p.qkv = ((k.img_qkv && mid) || (k.tp_img_qkv && tp_mid)) ? QkvSel::IMG : (k.fuse_qkv && few) ? QkvSel::FULLK : QkvSel::SPLITK;
+    p.resid_ssq = k.fuse_norm && few;
+    p.gate_up = (k.img_o && k.img_gate_up && mid) ? GateSel::DEFERRED_NORM_IMG : p.resid_ssq ? GateSel::NORM_ON_LOAD
+              : (k.tp_img_gate && tp_mid) ? GateSel::DIRECT_IMG : GateSel::DIRECT;
+    p.o = (k.tp_pub_o && pub) ? OSel::PUBLISH
+        : (k.img_o && mid) ? (p.gate_up == GateSel::DEFERRED_NORM_IMG ? OSel::IMG_PRENORM : OSel::IMG)
+        : (k.fuse_o && few) ? OSel::FULLK : OSel::SPLITK;
+    p.down = (k.fuse_down && few) ? DownSel::FULLK : (k.tp_pub_down && pub) ? DownSel::PUBLISH
+           : ((p.gate_up == GateSel::DEFERRED_NORM_IMG && k.img_down) || (k.tp_img_down && tp_mid)) ? DownSel::QUARTERS : DownSel::SPLITK;
+    p.xn_is_image = p.qkv == QkvSel::IMG;
+    p.attn_is_image = p.o == OSel::PUBLISH || p.o == OSel::IMG_PRENORM || p.o == OSel::IMG;
+    p.gate_in_is_image = p.gate_up == GateSel::DEFERRED_NORM_IMG || p.gate_up == GateSel::DIRECT_IMG;
+    p.act_is_image = p.down == DownSel::PUBLISH || p.down == DownSel::QUARTERS;
+    // can every producer write what its consumer reads?  plan_launches steps such configs down itself; this guards a planner change that forgets to
+    const bool ar_tail = p.meet == MeetSel::FUSED_AR && (p.o == OSel::PUBLISH || p.o == OSel::SPLITK);   // the all-reduce launch writes either layout
+    const char* bad =
+        p.xn_is_image && p.meet == MeetSel::EXT ? "QKV on an image behind the external transport's row-major norm" :
+        p.resid_ssq && !(p.qkv == QkvSel::FULLK && p.o == OSel::FULLK && p.down == DownSel::FULLK) ? "norm on load without the full-K launches that leave the sums of squares" :
+        (p.gate_up == GateSel::DEFERRED_NORM_IMG) != (p.o == OSel::IMG_PRENORM) ? "deferred norm in gate_up without the O launch that prepares it" :
+        p.gate_up == GateSel::DIRECT_IMG && !ar_tail ? "gate_up on an image no launch writes" :
+        p.act_is_image && p.gate_up == GateSel::NORM_ON_LOAD ? "down on an image behind a gate_up launch without image output" :
+        !p.act_is_image && p.gate_up == GateSel::DEFERRED_NORM_IMG && d->cfg.act_dtype == MI355_ACT_BF16 ? "bf16: gate_up image entry only with an image output" : nullptr;
+    if (bad) { mi355_set_error("decoder_begin: inconsistent launch plan for %d rows: %s", B, bad); return MI355_ERR_UNSUPPORTED; }
+    d->plan = p;
+    return MI355_OK;
+}
+
+// ---- where the partial sums of a row-parallel linear, the residual and the next RMSNorm meet (StepPlan::meet).  y: the normed rows, an image
+// if y_image; next_w: the linear behind the norm (TP: its shard is prefetched under the exchange).  Here: ns fp32 slabs in d->partials
+int meet_slabs(mi355_decoder* d, hipStream_t st, int ns, int n_pad, const void* norm_w, const mi355_weight_t* next_w, void* y, bool y_image,
+               const mi355_touch_t* touch) {
+    const auto& c = d->cfg; const int B = d->B;
+    switch (d->plan.meet) {
+    case MeetSel::LOCAL:
+        if (y_image) RUN(MI355_KC_NORM, mi355_add_rmsnorm_img_touch(nullptr, d->partials, ns, n_pad, nullptr, d->resid, d->resid, norm_w, c.rms_eps, B, c.hidden, y, ADT, touch, st));
+        else RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(nullptr, d->partials, ns, n_pad, nullptr, d->resid, d->resid, norm_w, c.rms_eps, B, c.hidden, y, ADT, st));
+        break;
+    case MeetSel::FUSED_AR:   // split-K reduce + all-reduce + residual + norm in one launch
+        RUN(MI355_KC_COMM, comm_with_prefetch(d, st, next_w, [&]() {
+            return (y_image ? mi355_allreduce_fused_img_dt : mi355_allreduce_fused_dt)(d->ar, nullptr, d->partials, ns, n_pad, nullptr, d->resid, d->resid,
+                                                                                      norm_w, c.rms_eps, B, c.hidden, y, ADT, st); }));
+        break;
+    case MeetSel::EXT:        // local split-K reduce -> 16-bit tensor for the TP all-reduce; residual + norm open the next segment
+        RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(nullptr, d->partials, ns, n_pad, nullptr, nullptr, d->bufs.ar_buf, nullptr, c.rms_eps, B, c.hidden, nullptr, ADT, st));
+        RUN(MI355_KC_COMM, ext_all_reduce(d, d->bufs.ar_buf, (size_t)B * c.hidden, st));
+        break;
+    }
+    return MI355_OK;
+}
+// the rank's rows already published in the all-reduce buffer (mi355_linear_publish_img): exchange + residual + norm
+int meet_published(mi355_decoder* d, hipStream_t st, const void* norm_w, const mi355_weight_t* next_w, void* y, bool y_image) {
+    RUN(MI355_KC_COMM, comm_with_prefetch(d, st, next_w, [&]() {
+        return mi355_allreduce_fused_published_dt(d->ar, d->resid, d->resid, norm_w, d->cfg.rms_eps, d->B, d->cfg.hidden, y, y_image ? 1 : 0, ADT, st); }));
+    return MI355_OK;
+}
+// external transport / segment caller: the all-reduced partial sums wait in ar_buf; residual + norm open the next segment
+int meet_ext_tail(mi355_decoder* d, hipStream_t st, const void* norm_w) {
+    RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(d->bufs.ar_buf, nullptr, 0, 0, nullptr, d->resid, d->resid, norm_w, d->cfg.rms_eps, d->B, d->cfg.hidden, d->xn, ADT, st));
+    return MI355_OK;
+}
+} // namespace
+
 extern "C" void mi355_decoder_destroy(mi355_decoder_t* d) {
     if (!d) return;
-    for (auto& kv : d->graphs) hipGraphExecDestroy(kv.second);
+    drop_graphs(d);
     if (d->cap_stream) hipStreamDestroy(d->cap_stream);
     if (d->side_stream) hipStreamDestroy(d->side_stream);
     if (d->ev_fork) hipEventDestroy(d->ev_fork);
@@ -400,9 +564,10 @@ extern "C" int mi355_decoder_begin_rows(mi355_decoder_t* d, int32_t nseq, int32_
                         "(larger batches: mi355_decoder_step)", nseq, q_len);
         return MI355_ERR_ARG;
     }
+    if (int e = resolve_step(d, B)) return e;
     hipStream_t st = (hipStream_t)stream;
     d->B = B; d->q_len = q_len; d->started = true;
-    const auto& c = d->cfg;
+    const auto& c = d->cfg; const StepPlan& p = d->plan;
     if (d->embed_split) {   // hidden-split table: this rank's columns, then the ranks' slices side by side
         const int n = c.hidden / c.tp_size;
         RUN(MI355_KC_OTHER, mi355_embedding(d->bufs.token_ids, B, d->model.embedding, n, d->model.vocab_full, d->act, st));
@@ -410,30 +575,21 @@ extern "C" int mi355_decoder_begin_rows(mi355_decoder_t* d, int32_t nseq, int32_
     } else {
         RUN(MI355_KC_OTHER, mi355_embedding(d->bufs.token_ids, B, d->model.embedding, c.hidden, d->model.vocab_full, d->resid, st));
     }
-    if (c.tp_size == 1 || d->ar) {
-        if ((d->img_qkv && B > d->fuse_rows) || (d->tp_img_qkv && d->ar && B > d->tp_fuse_rows))
-            RUN(MI355_KC_NORM, mi355_add_rmsnorm_img(d->resid, nullptr, 0, 0, nullptr, nullptr, nullptr, d->layers[0].input_norm, c.rms_eps, B,
-                                                     c.hidden, d->xn_img, ADT, st));
-        else
-            RUN(MI355_KC_NORM, mi355_rmsnorm_dt(d->resid, d->layers[0].input_norm, c.rms_eps, B, c.hidden, d->xn, ADT, st));
-    }
+    if (p.meet == MeetSel::EXT) return MI355_OK;   // the first segment norms its own rows
+    if (p.xn_is_image)
+        RUN(MI355_KC_NORM, mi355_add_rmsnorm_img(d->resid, nullptr, 0, 0, nullptr, nullptr, nullptr, d->layers[0].input_norm, c.rms_eps, B, c.hidden, d->xn_img, ADT, st));
+    else
+        RUN(MI355_KC_NORM, mi355_rmsnorm_dt(d->resid, d->layers[0].input_norm, c.rms_eps, B, c.hidden, d->xn, ADT, st));
     return MI355_OK;
 }
 
 extern "C" int mi355_decoder_attach_allreduce(mi355_decoder_t* d, mi355_allreduce_t* ar, int32_t vocab_offset) {
     if (!d || !ar || d->cfg.tp_size <= 1 || vocab_offset < 0) {
-        mi355_set_error("decoder_attach_allreduce: needs a decoder created with tp_size > 1 and an opened context");
-        return MI355_ERR_ARG;
+        mi355_set_error("decoder_attach_allreduce: needs a decoder created with tp_size > 1 and an opened context"); return MI355_ERR_ARG;
     }
-    for (auto& kv : d->graphs) hipGraphExecDestroy(kv.second);   // graphs captured for the segmented path are stale now
-    d->graphs.clear();
+    drop_graphs(d);   // graphs captured for the segmented path are stale now
     d->ar = ar; d->vocab_offset = vocab_offset;
-    if (!d->side_stream) {
-        d->overlap = hipStreamCreateWithFlags(&d->side_stream, hipStreamNonBlocking) == hipSuccess &&
-                     hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming) == hipSuccess &&
-                     hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming) == hipSuccess;
-        (void)hipGetLastError();
-    }
+    if (!d->side_stream) d->overlap = side_ready(d);
     return MI355_OK;
 }
 
@@ -441,12 +597,10 @@ extern "C" int mi355_decoder_attach_collective(mi355_decoder_t* d, const mi355_c
     if (!d || !coll || d->cfg.tp_size <= 1 || vocab_offset < 0 || !coll->all_reduce_f16 || !coll->all_gather ||
         coll->world != d->cfg.tp_size || coll->rank < 0 || coll->rank >= coll->world ||
         (d->cfg.act_dtype == MI355_ACT_BF16 && !coll->all_reduce_bf16)) {
-        mi355_set_error("decoder_attach_collective: needs a decoder created with tp_size > 1 and a transport of that world size");
-        return MI355_ERR_ARG;
+        mi355_set_error("decoder_attach_collective: needs a decoder created with tp_size > 1 and a transport of that world size"); return MI355_ERR_ARG;
     }
     if (d->ar) { mi355_set_error("decoder_attach_collective: an all-reduce context is already attached"); return MI355_ERR_ARG; }
-    for (auto& kv : d->graphs) hipGraphExecDestroy(kv.second);
-    d->graphs.clear();
+    drop_graphs(d);
     if (!d->pairs_local) {
         const size_t one = align256((size_t)d->cfg.max_batch * 8);
         if (hipMalloc(&d->pairs_local, one * (1 + (size_t)coll->world)) != hipSuccess) {
@@ -458,154 +612,58 @@ extern "C" int mi355_decoder_attach_collective(mi355_decoder_t* d, const mi355_c
     return MI355_OK;
 }
 
-namespace {
-// in-place sum of `count` fp16 over the TP ranks through the attached transport (no-op without one: the segment caller
-// all-reduces ar_buf itself between the calls)
-int ext_all_reduce(mi355_decoder* d, void* buf, size_t count, hipStream_t st) {
-    if (!d->has_ext) return MI355_OK;
-    const int rc = (d->cfg.act_dtype == MI355_ACT_BF16 ? d->ext.all_reduce_bf16 : d->ext.all_reduce_f16)(d->ext.ctx, buf, count, (mi355_stream_t)st);
-    if (rc != 0) { mi355_set_error("decoder: the attached transport's all-reduce failed (%d)", rc); return MI355_ERR_HIP; }
-    return MI355_OK;
-}
-} // namespace
-
 extern "C" int mi355_decoder_set_embedding_split(mi355_decoder_t* d, int32_t on) {
     if (!d || (on && (!d->ar || d->cfg.tp_size <= 1 || d->cfg.hidden % (8 * d->cfg.tp_size) != 0))) {
-        mi355_set_error("decoder_set_embedding_split: needs an attached all-reduce context and hidden %% (8 tp) == 0");
-        return MI355_ERR_ARG;
+        mi355_set_error("decoder_set_embedding_split: needs an attached all-reduce context and hidden %% (8 tp) == 0"); return MI355_ERR_ARG;
     }
-    for (auto& kv : d->graphs) hipGraphExecDestroy(kv.second);   // captured steps bake the embedding path in
-    d->graphs.clear();
+    drop_graphs(d);
     d->embed_split = on != 0;
     return MI355_OK;
 }
 
-namespace {
-constexpr size_t kPfInLaunchCap = (size_t)8 << 20;   // MI355_PF_TP_INLAUNCH: bytes of the next shard one all-reduce launch requests (the
-                                                     // peer reads of its reduction queue behind them: vmcnt returns in order)
-// all-reduce on `st`, prefetch of the next GEMM's weights on the side stream, joined before the GEMM (fork / join are
-// plain event edges, so the pair is captured into the step graph like everything else)
-template <class F>
-int comm_with_prefetch(mi355_decoder* d, hipStream_t st, const mi355_weight_t* next_w, F&& comm) {
-    const bool ov = d->overlap && (d->pf_mask & MI355_PF_TP_COMM) && next_w && next_w->qweight;
-    if ((d->pf_mask & MI355_PF_TP_INLAUNCH) && d->ar && next_w && next_w->qweight) {
-        // no second stream: the waves of the fused all-reduce launch that only wait for the peers' flags request the shard
-        const size_t bytes = (size_t)next_w->K_pad * next_w->N_pad * next_w->wbits / 8;
-        const int rc = mi355_allreduce_set_prefetch(d->ar, next_w->qweight, bytes < kPfInLaunchCap ? bytes : kPfInLaunchCap);
-        if (rc < 0) return rc;
-    }
-    if (ov) {
-        const size_t bytes = (size_t)next_w->K_pad * next_w->N_pad * next_w->wbits / 8;
-        if (hipEventRecord(d->ev_fork, st) != hipSuccess || hipStreamWaitEvent(d->side_stream, d->ev_fork, 0) != hipSuccess) {
-            mi355_set_error("decoder: fork to the side stream failed: %s", hipGetErrorString(hipGetLastError()));
-            return MI355_ERR_HIP;
-        }
-        // the last dword of the oob block is never read by anyone: a harmless sink
-        const int rc = mi355_prefetch(next_w->qweight, bytes < ((size_t)48 << 20) ? bytes : ((size_t)48 << 20), d->oob_count + 32, d->side_stream);
-        if (rc < 0) return rc;
-    }
-    const int rc = comm();
-    if (rc < 0) return rc;
-    if (ov && (hipEventRecord(d->ev_join, d->side_stream) != hipSuccess || hipStreamWaitEvent(st, d->ev_join, 0) != hipSuccess)) {
-        mi355_set_error("decoder: join of the side stream failed: %s", hipGetErrorString(hipGetLastError()));
-        return MI355_ERR_HIP;
-    }
-    return rc;
-}
-} // namespace
-
-namespace {
-bool side_ready(mi355_decoder* d) {
-    if (d->side_stream) return d->ev_fork && d->ev_join;
-    const bool ok = hipStreamCreateWithFlags(&d->side_stream, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming) == hipSuccess;
-    (void)hipGetLastError();
-    return ok;
-}
-// fork: from this point of `st` on, the side stream pulls up to `cap` bytes of w into the Infinity Cache
-int pf_issue(mi355_decoder* d, hipStream_t st, const mi355_weight_t* w, size_t cap) {
-    if (!w || !w->qweight || d->pf_pending || !side_ready(d)) return MI355_OK;
-    size_t bytes = (size_t)w->K_pad * w->N_pad * w->wbits / 8;
-    if (bytes > cap) bytes = cap;
-    if (hipEventRecord(d->ev_fork, st) != hipSuccess || hipStreamWaitEvent(d->side_stream, d->ev_fork, 0) != hipSuccess) {
-        mi355_set_error("decoder: fork to the prefetch stream failed: %s", hipGetErrorString(hipGetLastError()));
-        return MI355_ERR_HIP;
-    }
-    const int rc = mi355_prefetch(w->qweight, bytes, d->oob_count + 32, d->side_stream);
-    if (rc < 0) return rc;
-    if (hipEventRecord(d->ev_join, d->side_stream) != hipSuccess) {
-        mi355_set_error("decoder: prefetch stream event failed: %s", hipGetErrorString(hipGetLastError()));
-        return MI355_ERR_HIP;
-    }
-    d->pf_pending = true;
-    return MI355_OK;
-}
-// join: launches issued on `st` after this point wait for the prefetch in flight (it has normally long finished)
-int pf_join(mi355_decoder* d, hipStream_t st) {
-    if (!d->pf_pending) return MI355_OK;
-    d->pf_pending = false;
-    if (hipStreamWaitEvent(st, d->ev_join, 0) != hipSuccess) {
-        mi355_set_error("decoder: join of the prefetch stream failed: %s", hipGetErrorString(hipGetLastError()));
-        return MI355_ERR_HIP;
-    }
-    return MI355_OK;
-}
-constexpr size_t kPfCap = (size_t)48 << 20;
-} // namespace
-
 extern "C" int mi355_decoder_set_weight_prefetch(mi355_decoder_t* d, int32_t mask) {
     if (!d || mask < 0) { mi355_set_error("decoder_set_weight_prefetch: bad argument"); return MI355_ERR_ARG; }
-    for (auto& kv : d->graphs) hipGraphExecDestroy(kv.second);   // captured steps bake the fork / join edges in
-    d->graphs.clear();
-    if ((mask & ~(MI355_PF_TP_INLAUNCH | MI355_PF_QKV_IN_FOLD)) != 0 && !side_ready(d)) {   // the side stream and its events exist before any capture begins (not lazily inside one)
-        mi355_set_error("decoder_set_weight_prefetch: cannot create the prefetch stream: %s", hipGetErrorString(hipGetLastError()));
-        return MI355_ERR_HIP;
+    drop_graphs(d);
+    if ((mask & ~(MI355_PF_TP_INLAUNCH | MI355_PF_QKV_IN_FOLD)) != 0 && !side_ready(d)) {
+        mi355_set_error("decoder_set_weight_prefetch: cannot create the prefetch stream: %s", hipGetErrorString(hipGetLastError())); return MI355_ERR_HIP;
     }
     d->pf_mask = mask;
     return MI355_OK;
 }
 
-// does the attached context take published rows for a B-row call right now?  (host-side: not while it is on the granule protocol)
-static bool pub_ready(const mi355_decoder_t* d, int B) {
-    mi355_publish_target_t t;
-    return d->ar && mi355_allreduce_publish_target(d->ar, B, d->cfg.hidden, &t) == MI355_OK;
-}
-
 extern "C" int mi355_decoder_layer_attn(mi355_decoder_t* d, int32_t l, mi355_stream_t stream) {
     if (!d || l < 0 || l >= d->cfg.num_layers || d->B <= 0) { mi355_set_error("decoder_layer_attn: layer=%d", l); return MI355_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    const auto& c = d->cfg; const auto& L = d->layers[l]; const int B = d->B;
-    if (c.tp_size > 1 && !d->ar) {
+    const auto& c = d->cfg; const auto& L = d->layers[l]; const int B = d->B; const StepPlan& p = d->plan;
+    if (p.meet == MeetSel::EXT) {
         if (l == 0) RUN(MI355_KC_NORM, mi355_rmsnorm_dt(d->resid, L.input_norm, c.rms_eps, B, c.hidden, d->xn, ADT, st));
-        else RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(d->bufs.ar_buf, nullptr, 0, 0, nullptr, d->resid, d->resid, L.input_norm,
-                                                   c.rms_eps, B, c.hidden, d->xn, ADT, st));
+        else if (int e = meet_ext_tail(d, st, L.input_norm)) return e;
     }
     int ns = 0;
     mi355_kv_layer_t kv = kv_of(d, l);
-    const bool tp_img = d->tp_img_qkv && d->ar && B > d->tp_fuse_rows;   // TP: the QKV shard on the image the all-reduce launch wrote
-    const bool small = tp_img ? false : B <= d->fuse_rows;
-    const bool normed = small && d->fuse_norm;            // no norm launches in this step: see fuse_norm
-    const int pf = c.tp_size == 1 ? d->pf_mask : 0;       // (tp > 1: the side stream belongs to comm_with_prefetch)
-    if (int e = pf_join(d, st)) return e;                  // this layer's QKV weights, requested behind the previous down GEMM
-    const bool mid_qkv = (d->img_qkv && B > d->fuse_rows) || tp_img, mid_o = d->img_o && B > d->fuse_rows;   // 1-64 rows: full-K launches on activation images
-    if (mid_qkv) {
+    const int pf = p.meet == MeetSel::LOCAL ? d->pf_mask : 0;   // (tp > 1: the side stream belongs to comm_with_prefetch)
+    if (int e = pf_join(d, st)) return e;                        // this layer's QKV weights, requested behind the previous down GEMM
+    switch (p.qkv) {
+    case QkvSel::IMG:
         RUN(MI355_KC_GEMM_QUANT, mi355_qkv_rope_kv_write_img(d->xn_img, B, &L.qkv, L.qkv_bias, d->model.cos_sin, c.rope_dim, c.max_pos,
                                                              d->bufs.positions, d->bufs.block_table, c.max_blocks_per_seq, d->q_len, c.nh,
                                                              &kv, d->q_buf, d->oob_count, st));
-        if (pf & (MI355_PF_O | MI355_PF_O_LATE)) if (int e = pf_issue(d, st, &L.o, kPfCap)) return e;
-    } else if (d->fuse_qkv && small) {
+        PF_ISSUE(MI355_PF_O | MI355_PF_O_LATE, &L.o);
+        break;
+    case QkvSel::FULLK: {
         // layer 0 reads the rows mi355_decoder_begin normed; later layers normalise the residual rows on load
-        const mi355_fused_norm_t fn = {d->ssq, c.hidden / 16, (c.hidden / 16 + 3) & ~3, L.input_norm, c.rms_eps};
-        const bool on_load = normed && l > 0;
+        const mi355_fused_norm_t fn = {d->ssq, c.hidden / 16, ssq_pitch(c), L.input_norm, c.rms_eps};
+        const bool on_load = p.resid_ssq && l > 0;
         RUN(MI355_KC_GEMM_QUANT, mi355_qkv_rope_kv_write(on_load ? d->resid : d->xn, B, &L.qkv, L.qkv_bias, on_load ? &fn : nullptr,
                                                          d->model.cos_sin, c.rope_dim, c.max_pos, d->bufs.positions,
                                                          d->bufs.block_table, c.max_blocks_per_seq, d->q_len, c.nh, &kv, d->q_buf,
                                                          d->oob_count, st));
-        if (pf & (MI355_PF_O | MI355_PF_O_LATE)) if (int e = pf_issue(d, st, &L.o, kPfCap)) return e;
-    } else {
+        PF_ISSUE(MI355_PF_O | MI355_PF_O_LATE, &L.o);
+        break;
+    }
+    case QkvSel::SPLITK:
         RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial(d->xn, B, &L.qkv, d->partials, kMaxSplits, st));
-        if (pf & MI355_PF_O) if (int e = pf_issue(d, st, &L.o, kPfCap)) return e;          // under RoPE + attention
+        PF_ISSUE(MI355_PF_O, &L.o);          // under RoPE + attention
         if (!d->q_norm.empty())   // Qwen3: per-head Q / K RMSNorm in the writer, between the bias add and the rotation
             RUN(MI355_KC_ROPE_KV, mi355_rope_kv_write_rows_qk_norm(nullptr, d->partials, ns, L.qkv.N_pad, L.qkv_bias, d->q_norm[l], d->k_norm[l],
                                                                    c.rms_eps, d->model.cos_sin, c.rope_dim, c.max_pos, d->bufs.positions,
@@ -615,144 +673,98 @@ extern "C" int mi355_decoder_layer_attn(mi355_decoder_t* d, int32_t l, mi355_str
             RUN(MI355_KC_ROPE_KV, mi355_rope_kv_write_rows(nullptr, d->partials, ns, L.qkv.N_pad, L.qkv_bias, d->model.cos_sin, c.rope_dim,
                                                            c.max_pos, d->bufs.positions, d->bufs.block_table, c.max_blocks_per_seq, B,
                                                            d->q_len, c.nh, &kv, d->q_buf, d->oob_count, st));
-        if (pf & MI355_PF_O_LATE) if (int e = pf_issue(d, st, &L.o, kPfCap)) return e;     // under attention only
+        PF_ISSUE(MI355_PF_O_LATE, &L.o);     // under attention only
+        break;
     }
     // q_len > 1: rows of one sequence share a pass over its KV, causal mask inside the page walk (is_target_verify)
-    if (tp_img && d->tp_pub_o && B <= 64 && pub_ready(d, B)) {   // TP: attention image -> O shard published in the all-reduce buffer -> exchange + residual + norm
-        RUN(MI355_KC_ATTN, mi355_paged_attn_rows_img(d->q_buf, &kv, d->bufs.block_table, c.max_blocks_per_seq, d->bufs.positions,
-                                                     B / d->q_len, d->q_len, c.nh, 1.0f / sqrtf((float)c.hd), c.max_seq_len, d->attn_img,
-                                                     d->attn_ws, d->attn_ws_bytes, st));
-        if (int e = pf_join(d, st)) return e;
-        RUN(MI355_KC_GEMM_QUANT, mi355_linear_publish_img(d->attn_img, B, &L.o, nullptr, d->ar, st));
-        const bool gimg = d->tp_img_gate;                   // (B > tp_fuse_rows holds: tp_img)
-        RUN(MI355_KC_COMM, comm_with_prefetch(d, st, &L.gate_up, [&]() {
-            return mi355_allreduce_fused_published_dt(d->ar, d->resid, d->resid, L.post_norm, c.rms_eps, B, c.hidden, gimg ? d->xg_img : d->xn, gimg ? 1 : 0, ADT, st); }));
-        return MI355_OK;
-    }
-    if (mid_o) {   // the attention output as an image: what the O projection's full-K launch reads
-        RUN(MI355_KC_ATTN, mi355_paged_attn_rows_img(d->q_buf, &kv, d->bufs.block_table, c.max_blocks_per_seq, d->bufs.positions,
-                                                     B / d->q_len, d->q_len, c.nh, 1.0f / sqrtf((float)c.hd), c.max_seq_len, d->attn_img,
-                                                     d->attn_ws, d->attn_ws_bytes, st));
-        if (int e = pf_join(d, st)) return e;
-        if (d->img_gate_up) {   // no norm launch: gate_up finishes the RMSNorm on its accumulators
-            RUN(MI355_KC_GEMM_QUANT, mi355_linear_residual_prenorm_img(d->attn_img, B, &L.o, nullptr, d->resid, d->resid, L.post_norm,
-                                                                       d->post_norm_exp[l], d->xg_img, d->ssq64, (c.hidden / 16 + 3) & ~3, st));
-            return MI355_OK;
-        }
-        RUN(MI355_KC_GEMM_QUANT, mi355_linear_residual_img(d->attn_img, B, &L.o, nullptr, d->resid, d->resid, nullptr, 0, st));
-        if (pf & MI355_PF_GATE_UP) if (int e = pf_issue(d, st, &L.gate_up, kPfCap)) return e;
-        RUN(MI355_KC_NORM, mi355_rmsnorm_dt(d->resid, L.post_norm, c.rms_eps, B, c.hidden, d->xn, ADT, st));
-        return MI355_OK;
-    }
-    RUN(MI355_KC_ATTN, mi355_paged_attn_rows(d->q_buf, &kv, d->bufs.block_table, c.max_blocks_per_seq, d->bufs.positions,
-                                             B / d->q_len, d->q_len, c.nh, 1.0f / sqrtf((float)c.hd), c.max_seq_len, d->attn_out,
-                                             d->attn_ws, d->attn_ws_bytes, st));
+    RUN(MI355_KC_ATTN, (p.attn_is_image ? mi355_paged_attn_rows_img : mi355_paged_attn_rows)(
+                           d->q_buf, &kv, d->bufs.block_table, c.max_blocks_per_seq, d->bufs.positions, B / d->q_len, d->q_len, c.nh,
+                           1.0f / sqrtf((float)c.hd), c.max_seq_len, p.attn_is_image ? d->attn_img : d->attn_out, d->attn_ws, d->attn_ws_bytes, st));
     if (int e = pf_join(d, st)) return e;
-    if (d->fuse_o && small) {     // h += fp16(attn W_o) in the GEMM's epilogue: no slabs; the norm moves into gate_up (or stays a launch)
-        RUN(MI355_KC_GEMM_QUANT, mi355_linear_residual(d->attn_out, B, &L.o, nullptr, d->resid, d->resid, normed ? d->ssq : nullptr, (c.hidden / 16 + 3) & ~3, st));
-        if (!normed) {
-            if (pf & MI355_PF_GATE_UP) if (int e = pf_issue(d, st, &L.gate_up, kPfCap)) return e;
-            RUN(MI355_KC_NORM, mi355_rmsnorm_dt(d->resid, L.post_norm, c.rms_eps, B, c.hidden, d->xn, ADT, st));
-        }
+    void* const gate_in = p.gate_in_is_image ? d->xg_img : d->xn;   // what this half leaves for gate_up (resid_ssq: the residual rows themselves)
+    switch (p.o) {
+    case OSel::PUBLISH:       // TP: O shard published in the all-reduce buffer -> exchange + residual + norm
+        RUN(MI355_KC_GEMM_QUANT, mi355_linear_publish_img(d->attn_img, B, &L.o, nullptr, d->ar, st));
+        return meet_published(d, st, L.post_norm, &L.gate_up, gate_in, p.gate_in_is_image);
+    case OSel::IMG_PRENORM:   // no norm launch: gate_up finishes the RMSNorm on its accumulators
+        RUN(MI355_KC_GEMM_QUANT, mi355_linear_residual_prenorm_img(d->attn_img, B, &L.o, nullptr, d->resid, d->resid, L.post_norm,
+                                                                   d->post_norm_exp[l], d->xg_img, d->ssq64, ssq_pitch(c), st));
         return MI355_OK;
+    case OSel::IMG:
+        RUN(MI355_KC_GEMM_QUANT, mi355_linear_residual_img(d->attn_img, B, &L.o, nullptr, d->resid, d->resid, nullptr, 0, st));
+        break;
+    case OSel::FULLK:         // h += fp16(attn W_o) in the GEMM's epilogue: no slabs; the norm moves into gate_up (or stays a launch)
+        RUN(MI355_KC_GEMM_QUANT, mi355_linear_residual(d->attn_out, B, &L.o, nullptr, d->resid, d->resid, p.resid_ssq ? d->ssq : nullptr, ssq_pitch(c), st));
+        if (p.resid_ssq) return MI355_OK;
+        break;
+    case OSel::SPLITK:
+        RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial(d->attn_out, B, &L.o, d->partials, kMaxSplits, st));
+        PF_ISSUE(MI355_PF_GATE_UP, &L.gate_up);   // under the reduce + norm launch
+        return meet_slabs(d, st, ns, L.o.N_pad, L.post_norm, &L.gate_up, gate_in, p.gate_in_is_image, nullptr);
     }
-    RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial(d->attn_out, B, &L.o, d->partials, kMaxSplits, st));
-    if (pf & MI355_PF_GATE_UP) if (int e = pf_issue(d, st, &L.gate_up, kPfCap)) return e;   // under the reduce + norm launch
-    if (c.tp_size == 1) {
-        RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(nullptr, d->partials, ns, L.o.N_pad, nullptr, d->resid, d->resid, L.post_norm,
-                                             c.rms_eps, B, c.hidden, d->xn, ADT, st));
-    } else if (d->ar) { // split-K reduce + all-reduce + residual + post-attention norm in one launch
-        const bool gimg = d->tp_img_gate && B > d->tp_fuse_rows;   // the gate_up shard reads an image (one launch, gemm_splitk64 direct form)
-        RUN(MI355_KC_COMM, comm_with_prefetch(d, st, &L.gate_up, [&]() {
-            return gimg ? mi355_allreduce_fused_img_dt(d->ar, nullptr, d->partials, ns, L.o.N_pad, nullptr, d->resid, d->resid, L.post_norm,
-                                                       c.rms_eps, B, c.hidden, d->xg_img, ADT, st)
-                        : mi355_allreduce_fused_dt(d->ar, nullptr, d->partials, ns, L.o.N_pad, nullptr, d->resid, d->resid, L.post_norm,
-                                         c.rms_eps, B, c.hidden, d->xn, ADT, st); }));
-    } else { // local split-K reduce -> fp16 tensor for the TP all-reduce
-        RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(nullptr, d->partials, ns, L.o.N_pad, nullptr, nullptr, d->bufs.ar_buf, nullptr,
-                                             c.rms_eps, B, c.hidden, nullptr, ADT, st));
-        RUN(MI355_KC_COMM, ext_all_reduce(d, d->bufs.ar_buf, (size_t)B * c.hidden, st));
-    }
+    PF_ISSUE(MI355_PF_GATE_UP, &L.gate_up);       // IMG, FULLK without the fused norm: the residual is complete, the norm stays a launch
+    RUN(MI355_KC_NORM, mi355_rmsnorm_dt(d->resid, L.post_norm, c.rms_eps, B, c.hidden, d->xn, ADT, st));
     return MI355_OK;
 }
 
 extern "C" int mi355_decoder_layer_mlp(mi355_decoder_t* d, int32_t l, mi355_stream_t stream) {
     if (!d || l < 0 || l >= d->cfg.num_layers || d->B <= 0) { mi355_set_error("decoder_layer_mlp: layer=%d", l); return MI355_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    const auto& c = d->cfg; const auto& L = d->layers[l]; const int B = d->B;
-    if (c.tp_size > 1 && !d->ar) {
-        RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(d->bufs.ar_buf, nullptr, 0, 0, nullptr, d->resid, d->resid, L.post_norm, c.rms_eps,
-                                             B, c.hidden, d->xn, ADT, st));
-    }
-    const bool small = B <= d->fuse_rows;
-    const bool normed = small && d->fuse_norm && d->fuse_o;
-    const int pf = c.tp_size == 1 ? d->pf_mask : 0;
+    const auto& c = d->cfg; const auto& L = d->layers[l]; const int B = d->B; const StepPlan& p = d->plan;
+    if (p.meet == MeetSel::EXT) if (int e = meet_ext_tail(d, st, L.post_norm)) return e;
+    const int pf = p.meet == MeetSel::LOCAL ? d->pf_mask : 0;
     if (int e = pf_join(d, st)) return e;
-    if (d->img_o && d->img_gate_up && B > d->fuse_rows) {   // the O launch left gamma 2^-e h' and the sums of h'^2: RMSNorm finished on gate_up's accumulators
-        const mi355_deferred_norm_t dn = {d->ssq64, c.hidden / 16, (c.hidden / 16 + 3) & ~3, c.rms_eps, ldexpf(1.f, d->post_norm_exp[l])};
-        const bool down_img = d->img_down;                 // gate_up's SiLU epilogue writes the image down_proj's K-quarter launch reads
-        RUN(MI355_KC_GEMM_QUANT, mi355_linear_deferred_norm_img(d->xg_img, B, &dn, &L.gate_up, nullptr, down_img ? d->act_img : d->act,
-                                                                MI355_EPI_SILU_MUL | (down_img ? MI355_EPI_OUT_IMAGE : 0), st));
-    } else if (normed) {   // post-attention RMSNorm on load + gate_up + SiLU-gate in one launch
-        const mi355_fused_norm_t fn = {d->ssq, c.hidden / 16, (c.hidden / 16 + 3) & ~3, L.post_norm, c.rms_eps};
-        RUN(MI355_KC_GEMM_QUANT, mi355_norm_linear(d->resid, B, &fn, &L.gate_up, nullptr, d->act, MI355_EPI_SILU_MUL, st));
-    } else {
-        const bool gi = d->tp_img_down && d->ar && B > d->tp_fuse_rows;   // TP: the SiLU output of the shard as the image the K-quarter down launch reads
-        if (gi && d->tp_img_gate)   // ... and the shard itself as one launch on the image the all-reduce behind the O shard wrote
-            RUN(MI355_KC_GEMM_QUANT, mi355_linear_direct_img(d->xg_img, B, &L.gate_up, nullptr, d->act_img, MI355_EPI_SILU_MUL | MI355_EPI_OUT_IMAGE, st));
-        else
-            RUN(MI355_KC_GEMM_QUANT, mi355_linear_direct(d->xn, B, &L.gate_up, nullptr, gi ? d->act_img : d->act, MI355_EPI_SILU_MUL | (gi ? MI355_EPI_OUT_IMAGE : 0),
-                                                     d->partials, d->partials_bytes, st));
+    void* const act = p.act_is_image ? d->act_img : d->act;   // gate_up's SiLU epilogue writes what the down launch reads
+    const int epi = MI355_EPI_SILU_MUL | (p.act_is_image ? MI355_EPI_OUT_IMAGE : 0);
+    switch (p.gate_up) {
+    case GateSel::DEFERRED_NORM_IMG: {   // the O launch left gamma 2^-e h' and the sums of h'^2: RMSNorm finished on gate_up's accumulators
+        const mi355_deferred_norm_t dn = {d->ssq64, c.hidden / 16, ssq_pitch(c), c.rms_eps, ldexpf(1.f, d->post_norm_exp[l])};
+        RUN(MI355_KC_GEMM_QUANT, mi355_linear_deferred_norm_img(d->xg_img, B, &dn, &L.gate_up, nullptr, act, epi, st));
+        break;
+    }
+    case GateSel::NORM_ON_LOAD: {        // post-attention RMSNorm on load + gate_up + SiLU-gate in one launch
+        const mi355_fused_norm_t fn = {d->ssq, c.hidden / 16, ssq_pitch(c), L.post_norm, c.rms_eps};
+        RUN(MI355_KC_GEMM_QUANT, mi355_norm_linear(d->resid, B, &fn, &L.gate_up, nullptr, act, epi, st));
+        break;
+    }
+    case GateSel::DIRECT_IMG:            // TP: the shard as one launch on the image the all-reduce behind the O shard wrote
+        RUN(MI355_KC_GEMM_QUANT, mi355_linear_direct_img(d->xg_img, B, &L.gate_up, nullptr, act, epi, st));
+        break;
+    case GateSel::DIRECT:
+        RUN(MI355_KC_GEMM_QUANT, mi355_linear_direct(d->xn, B, &L.gate_up, nullptr, act, epi, d->partials, d->partials_bytes, st));
+        break;
     }
     int ns = 0;
-    const void* next_norm = (l + 1 < c.num_layers) ? d->layers[l + 1].input_norm : d->model.final_norm;
-    const mi355_weight_t* next_qkv = (l + 1 < c.num_layers) ? &d->layers[l + 1].qkv : nullptr;
-    if (pf & MI355_PF_QKV) if (int e = pf_issue(d, st, next_qkv, kPfCap)) return e;         // under the down GEMM (+ norm)
-    if (d->fuse_down && small) {
-        const bool last = l + 1 == c.num_layers;          // the final norm feeds lm_head: that one stays a launch
-        RUN(MI355_KC_GEMM_QUANT, mi355_linear_residual(d->act, B, &L.down, nullptr, d->resid, d->resid, (normed && !last) ? d->ssq : nullptr, (c.hidden / 16 + 3) & ~3, st));
-        if (!normed || last) RUN(MI355_KC_NORM, mi355_rmsnorm_dt(d->resid, next_norm, c.rms_eps, B, c.hidden, d->xn, ADT, st));
+    const bool last = l + 1 == c.num_layers;             // the final norm feeds lm_head: row-major, and always a launch
+    const void* next_norm = last ? d->model.final_norm : d->layers[l + 1].input_norm;
+    const mi355_weight_t* next_qkv = last ? nullptr : &d->layers[l + 1].qkv;
+    const mi355_weight_t* next_w = last ? &d->model.lm_head : next_qkv;
+    const bool y_image = p.xn_is_image && !last;
+    void* const y = y_image ? d->xn_img : d->xn;
+    PF_ISSUE(MI355_PF_QKV, next_qkv);                    // under the down GEMM (+ norm)
+    switch (p.down) {
+    case DownSel::FULLK: {
+        const bool ssq = p.resid_ssq && !last;
+        RUN(MI355_KC_GEMM_QUANT, mi355_linear_residual(d->act, B, &L.down, nullptr, d->resid, d->resid, ssq ? d->ssq : nullptr, ssq_pitch(c), st));
+        if (!ssq) RUN(MI355_KC_NORM, mi355_rmsnorm_dt(d->resid, next_norm, c.rms_eps, B, c.hidden, d->xn, ADT, st));
         return MI355_OK;
     }
-    if (d->tp_pub_down && d->ar && B > d->tp_fuse_rows && B <= 64 && pub_ready(d, B)) {   // TP: the down shard published in the all-reduce buffer (act_img: written above, gi)
+    case DownSel::PUBLISH:   // TP: the down shard published in the all-reduce buffer
         RUN(MI355_KC_GEMM_QUANT, mi355_linear_publish_img(d->act_img, B, &L.down, nullptr, d->ar, st));
-        const mi355_weight_t* next_w = (l + 1 < c.num_layers) ? &d->layers[l + 1].qkv : &d->model.lm_head;
-        const bool next_img = d->tp_img_qkv && l + 1 < c.num_layers;
-        RUN(MI355_KC_COMM, comm_with_prefetch(d, st, next_w, [&]() {
-            return mi355_allreduce_fused_published_dt(d->ar, d->resid, d->resid, next_norm, c.rms_eps, B, c.hidden, next_img ? d->xn_img : d->xn, next_img ? 1 : 0, ADT, st); }));
-        return MI355_OK;
-    }
-    if ((d->img_o && d->img_gate_up && d->img_down && B > d->fuse_rows) || (d->tp_img_down && d->ar && B > d->tp_fuse_rows))
+        return meet_published(d, st, next_norm, next_w, y, y_image);
+    case DownSel::QUARTERS:
         RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial_img(d->act_img, B, &L.down, d->partials, kMaxSplits, st));
-    else
+        break;
+    case DownSel::SPLITK:
         RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial(d->act, B, &L.down, d->partials, kMaxSplits, st));
-    if (pf & MI355_PF_QKV_LATE) if (int e = pf_issue(d, st, next_qkv, kPfCap)) return e;    // under the reduce + norm launch only
-    if (c.tp_size == 1) {
-        if (d->img_qkv && B > d->fuse_rows && l + 1 < c.num_layers)   // the next layer's QKV launch reads an image (the final norm feeds lm_head: row-major)
-        {   // the fold runs on B of the 256 CUs: its spare blocks touch the NEXT layer's QKV weights (MI355_PF_QKV_IN_FOLD, internal.h mi355_touch_t)
-            mi355_touch_t tc; const mi355_touch_t* touch = nullptr;
-            if ((d->pf_mask & MI355_PF_QKV_IN_FOLD) && l + 1 < c.num_layers &&
-                mi355_qkv_touch_plan(&d->layers[l + 1].qkv, c.hd, d->oob_count + 32, &tc) == MI355_OK) touch = &tc;
-            RUN(MI355_KC_NORM, mi355_add_rmsnorm_img_touch(nullptr, d->partials, ns, L.down.N_pad, nullptr, d->resid, d->resid, next_norm,
-                                                           c.rms_eps, B, c.hidden, d->xn_img, ADT, touch, st));
-        }
-        else
-            RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(nullptr, d->partials, ns, L.down.N_pad, nullptr, d->resid, d->resid, next_norm,
-                                                 c.rms_eps, B, c.hidden, d->xn, ADT, st));
-    } else if (d->ar) {
-        const mi355_weight_t* next_w = (l + 1 < c.num_layers) ? &d->layers[l + 1].qkv : &d->model.lm_head;
-        const bool next_img = d->tp_img_qkv && B > d->tp_fuse_rows && l + 1 < c.num_layers;   // the next layer's QKV shard reads an image (the final norm feeds lm_head: row-major)
-        RUN(MI355_KC_COMM, comm_with_prefetch(d, st, next_w, [&]() {
-            return next_img ? mi355_allreduce_fused_img_dt(d->ar, nullptr, d->partials, ns, L.down.N_pad, nullptr, d->resid, d->resid, next_norm,
-                                                           c.rms_eps, B, c.hidden, d->xn_img, ADT, st)
-                            : mi355_allreduce_fused_dt(d->ar, nullptr, d->partials, ns, L.down.N_pad, nullptr, d->resid, d->resid, next_norm,
-                                         c.rms_eps, B, c.hidden, d->xn, ADT, st); }));
-    } else {
-        RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(nullptr, d->partials, ns, L.down.N_pad, nullptr, nullptr, d->bufs.ar_buf, nullptr,
-                                             c.rms_eps, B, c.hidden, nullptr, ADT, st));
-        RUN(MI355_KC_COMM, ext_all_reduce(d, d->bufs.ar_buf, (size_t)B * c.hidden, st));
+        break;
     }
-    return MI355_OK;
+    PF_ISSUE(MI355_PF_QKV_LATE, next_qkv);               // under the reduce + norm launch only
+    // tp = 1 image fold: it runs on B of the 256 CUs, its spare blocks touch the NEXT layer's QKV weights (MI355_PF_QKV_IN_FOLD, internal.h mi355_touch_t)
+    mi355_touch_t tc; const mi355_touch_t* touch = nullptr;
+    if (y_image && p.meet == MeetSel::LOCAL && (d->pf_mask & MI355_PF_QKV_IN_FOLD) &&
+        mi355_qkv_touch_plan(next_qkv, c.hd, d->oob_count + 32, &tc) == MI355_OK) touch = &tc;
+    return meet_slabs(d, st, ns, L.down.N_pad, next_norm, next_w, y, y_image, touch);
 }
 
 // Dynamic-NTK RoPE (rotary_position_embedding.h:889-951) in PREFILL: context_rope (:1000-1025) rotates every token of the batch with ONE base, that of
@@ -819,6 +831,18 @@ size_t carve_prefill(const mi355_model_config_t& c, int T, int nseq, void* base,
     if (out) *out = b;
     return cv.off;
 }
+
+// a row-parallel linear's T rows in b.tmp: (all-reduce +) residual + RMSNorm(norm_w) -> b.xn
+int prefill_meet(mi355_decoder* d, hipStream_t st, const PrefillBufs& b, int T, const void* norm_w) {
+    const auto& c = d->cfg;
+    if (c.tp_size > 1 && d->ar) {
+        RUN(MI355_KC_COMM, mi355_allreduce_fused_dt(d->ar, b.tmp, nullptr, 0, 0, nullptr, b.resid, b.resid, norm_w, c.rms_eps, T, c.hidden, b.xn, ADT, st));
+        return MI355_OK;
+    }
+    if (c.tp_size > 1) RUN(MI355_KC_COMM, ext_all_reduce(d, b.tmp, (size_t)T * c.hidden, st));
+    RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(b.tmp, nullptr, 0, 0, nullptr, b.resid, b.resid, norm_w, c.rms_eps, T, c.hidden, b.xn, ADT, st));
+    return MI355_OK;
+}
 } // namespace
 
 extern "C" size_t mi355_decoder_prefill_workspace_bytes(mi355_decoder_t* d, int32_t max_tokens, int32_t max_seqs) {
@@ -866,23 +890,11 @@ extern "C" int mi355_decoder_prefill(mi355_decoder_t* d, const int32_t* token_id
         RUN(MI355_KC_ATTN, mi355_paged_attn_rows(b.q, &kv, block_table, c.max_blocks_per_seq, positions, nseq, q_len, c.nh, scale,
                                                  c.max_seq_len, b.attn, b.attn_ws, b.attn_ws_bytes, st));
         RUN(MI355_KC_GEMM_QUANT, mi355_linear_forward(b.attn, T, &L.o, nullptr, b.tmp, MI355_EPI_NONE, b.gemm_ws, b.gemm_ws_bytes, st));
-        if (c.tp_size > 1 && !d->ar) RUN(MI355_KC_COMM, ext_all_reduce(d, b.tmp, (size_t)T * c.hidden, st));
-        if (c.tp_size == 1 || !d->ar) {
-            RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(b.tmp, nullptr, 0, 0, nullptr, b.resid, b.resid, L.post_norm, c.rms_eps, T, c.hidden, b.xn, ADT, st));
-        } else {
-            RUN(MI355_KC_COMM, mi355_allreduce_fused_dt(d->ar, b.tmp, nullptr, 0, 0, nullptr, b.resid, b.resid, L.post_norm, c.rms_eps, T,
-                                                     c.hidden, b.xn, ADT, st));
-        }
+        if (int e = prefill_meet(d, st, b, T, L.post_norm)) return e;
         RUN(MI355_KC_GEMM_QUANT, mi355_linear_forward(b.xn, T, &L.gate_up, nullptr, b.act, MI355_EPI_SILU_MUL, b.gemm_ws, b.gemm_ws_bytes, st));
         RUN(MI355_KC_GEMM_QUANT, mi355_linear_forward(b.act, T, &L.down, nullptr, b.tmp, MI355_EPI_NONE, b.gemm_ws, b.gemm_ws_bytes, st));
         const void* next_norm = (l + 1 < c.num_layers) ? d->layers[l + 1].input_norm : d->model.final_norm;
-        if (c.tp_size > 1 && !d->ar) RUN(MI355_KC_COMM, ext_all_reduce(d, b.tmp, (size_t)T * c.hidden, st));
-        if (c.tp_size == 1 || !d->ar) {
-            RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(b.tmp, nullptr, 0, 0, nullptr, b.resid, b.resid, next_norm, c.rms_eps, T, c.hidden, b.xn, ADT, st));
-        } else {
-            RUN(MI355_KC_COMM, mi355_allreduce_fused_dt(d->ar, b.tmp, nullptr, 0, 0, nullptr, b.resid, b.resid, next_norm, c.rms_eps, T,
-                                                     c.hidden, b.xn, ADT, st));
-        }
+        if (int e = prefill_meet(d, st, b, T, next_norm)) return e;
     }
     if (logit_rows && logits_out) {   // gather the requested rows of the final normed hidden state, then lm_head on nseq rows
         RUN(MI355_KC_OTHER, mi355_embedding(logit_rows, nseq, b.xn, c.hidden, T, b.last_h, st));
@@ -906,28 +918,26 @@ int ext_argmax(mi355_decoder* d, int B, hipStream_t st) {
     RUN(MI355_KC_OTHER, mi355_argmax_pick(d->pairs_all, d->ext.world, B, d->bufs.token_ids, d->bufs.positions, st));
     return MI355_OK;
 }
+// greedy ids of B rows of logits -> token_ids (and positions + 1) for the next step
+int greedy_tail(mi355_decoder* d, int B, hipStream_t st) {
+    const auto& c = d->cfg;
+    if (d->ar)   // vocab-split lm_head: (max, index) pairs cross the ranks, not the logits
+        RUN(MI355_KC_COMM, mi355_allreduce_argmax(d->ar, d->bufs.logits, B, c.vocab, c.vocab, d->vocab_offset, d->bufs.token_ids,
+                                                  d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
+    else if (d->has_ext) return ext_argmax(d, B, st);
+    else RUN(MI355_KC_OTHER, mi355_argmax_ex(d->bufs.logits, B, c.vocab, c.vocab, d->bufs.token_ids, d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
+    return MI355_OK;
+}
 } // namespace
 
 extern "C" int mi355_decoder_finish(mi355_decoder_t* d, int32_t sample, mi355_stream_t stream) {
     if (!d || d->B <= 0) { mi355_set_error("decoder_finish: no step in flight"); return MI355_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    const auto& c = d->cfg; const int B = d->B;
+    const int B = d->B;
     if (int e = pf_join(d, st)) return e;
-    if (c.tp_size > 1 && !d->ar) {
-        RUN(MI355_KC_NORM, mi355_add_rmsnorm_dt(d->bufs.ar_buf, nullptr, 0, 0, nullptr, d->resid, d->resid, d->model.final_norm,
-                                             c.rms_eps, B, c.hidden, d->xn, ADT, st));
-    }
+    if (d->plan.meet == MeetSel::EXT) if (int e = meet_ext_tail(d, st, d->model.final_norm)) return e;
     RUN(MI355_KC_GEMM_LMHEAD, mi355_linear_direct(d->xn, B, &d->model.lm_head, nullptr, d->bufs.logits, MI355_EPI_OUT_F32, nullptr, 0, st));
-    if (sample && d->ar) {   // vocab-split lm_head: (max, index) pairs cross the ranks, not the logits
-        RUN(MI355_KC_COMM, mi355_allreduce_argmax(d->ar, d->bufs.logits, B, c.vocab, c.vocab, d->vocab_offset, d->bufs.token_ids,
-                                                  d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
-    } else if (sample && d->has_ext) {
-        if (int e = ext_argmax(d, B, st)) return e;
-    } else if (sample) {
-        RUN(MI355_KC_OTHER, mi355_argmax_ex(d->bufs.logits, B, c.vocab, c.vocab, d->bufs.token_ids, d->bufs.positions,
-                                            d->argmax_ws, d->argmax_ws_bytes, st));
-    }
-    return MI355_OK;
+    return sample ? greedy_tail(d, B, st) : MI355_OK;
 }
 
 extern "C" int mi355_decoder_step(mi355_decoder_t* d, int32_t B, mi355_stream_t stream) {
@@ -937,21 +947,9 @@ extern "C" int mi355_decoder_step(mi355_decoder_t* d, int32_t B, mi355_stream_t 
     }
     if (B > 64) {   // large batch: the generic path (large-M GEMMs, fp16 intermediates), one row per sequence
         if (B > d->cfg.max_batch) { mi355_set_error("decoder_step: B=%d > max_batch", B); return MI355_ERR_ARG; }
-        hipStream_t st = (hipStream_t)stream;
-        const auto& c = d->cfg;
-        int rc = mi355_decoder_prefill(d, d->bufs.token_ids, d->bufs.positions, d->bufs.block_table, B, 1, d->iota, d->bufs.logits,
-                                       d->wide_ws, d->wide_ws_bytes, stream);
-        if (rc < 0) return rc;
-        if (d->ar) {
-            RUN(MI355_KC_COMM, mi355_allreduce_argmax(d->ar, d->bufs.logits, B, c.vocab, c.vocab, d->vocab_offset, d->bufs.token_ids,
-                                                      d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
-        } else if (d->has_ext) {
-            if (int e = ext_argmax(d, B, st)) return e;
-        } else {
-            RUN(MI355_KC_OTHER, mi355_argmax_ex(d->bufs.logits, B, c.vocab, c.vocab, d->bufs.token_ids, d->bufs.positions, d->argmax_ws,
-                                                d->argmax_ws_bytes, st));
-        }
-        return MI355_OK;
+        const int rc = mi355_decoder_prefill(d, d->bufs.token_ids, d->bufs.positions, d->bufs.block_table, B, 1, d->iota, d->bufs.logits,
+                                             d->wide_ws, d->wide_ws_bytes, stream);
+        return rc < 0 ? rc : greedy_tail(d, B, (hipStream_t)stream);
     }
     int rc = mi355_decoder_begin(d, B, stream);
     for (int l = 0; rc >= 0 && l < d->cfg.num_layers; ++l) {
