@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MI355_ABI_VERSION 3
+#define MI355_ABI_VERSION 4
 
 typedef void* mi355_stream_t; /* hipStream_t */
 
@@ -181,13 +181,27 @@ int mi355_embedding(const int32_t* ids, int32_t T, const void* table, int32_t H,
  * (per-layer tensor [blocks, 2, nkv, page, hd], K block = pool index 2b,
  * V block = 2b+1: bindings/OpDefs.h:24-28,201-202, kv_cache_kernels.cu:58-61;
  * 8-bit scale plane fp32 [blocks][2][nkv][page]: kv_cache_utils.h:265-271,
- * MHAKVCacheSpec.h:52-54,82-92).  Intra-block layout is native:
- *   K block: [nkv][page][hd]       (token-major, hd contiguous)
- *   V block: [nkv][hd][page]       (channel-major: the MFMA k-dim of P.V is
- *                                   tokens, so tokens are contiguous per channel —
- *                                   same as the reference's NonAsm V layout,
- *                                   kv_cache_utils.h:236-241)
+ * MHAKVCacheSpec.h:52-54,82-92).  The layout INSIDE a block is a property of the cache (`layout`), so that a pool the
+ * reference's own ops wrote (its prefill op, block reuse, prefix caching) can be read and extended in place:
+ *   MI355_KV_LAYOUT_NATIVE (0, the default)
+ *     K block: [nkv][page][hd]       (token-major, hd contiguous)
+ *     V block: [nkv][hd][page]       (channel-major: the MFMA k-dim of P.V is tokens, so tokens are contiguous per channel)
+ *   MI355_KV_LAYOUT_REF       the reference's layout with the linear V of its NonAsm / V1 decode back-end
+ *     K block: [nkv][hd/x][page][x]  (x = 16 / element bytes = 8; kv_cache_utils.h:209-243)
+ *     V block: [nkv][hd][page]
+ *   MI355_KV_LAYOUT_REF_VVEC  the same K with the vectorised V of the reference's Asm back-end
+ *     V block: [nkv][page/x][hd][x]
+ * Element offset inside one head's page * hd elements, token t of the page, channel d:
+ *     layout     K                              V
+ *     NATIVE     t*hd + d                       d*page + t
+ *     REF        ((d/x)*page + t)*x + d%x       d*page + t
+ *     REF_VVEC   as REF                         ((t/x)*hd + d)*x + t%x
+ * Pool indexing (K = 2b, V = 2b+1, nkv heads per block) is the same for all three.  The non-native layouts take the 16-bit
+ * caches (MI355_KV_FP16 / MI355_KV_BF16) with hd 64 / 128 and page 16 / 32 / 64; with MI355_KV_INT8, or with an unknown layout
+ * value, every entry point returns MI355_ERR_ARG before it launches anything (the reference has no INT8-KV writer whose bytes
+ * could be shared, and our codes are offset-binary).  The same launches serve every layout: only addresses differ.
  * ---------------------------------------------------------------------- */
+enum { MI355_KV_LAYOUT_NATIVE = 0, MI355_KV_LAYOUT_REF = 1, MI355_KV_LAYOUT_REF_VVEC = 2 };
 typedef struct {
     void*   kv_base;    /* dev: fp16 or int8 elements */
     float*  scale_base; /* dev: INT8 only, else NULL */
@@ -198,6 +212,7 @@ typedef struct {
     int32_t num_blocks;
     int32_t act_dtype;  /* dtype of Q / K / V rows and of the attention output: MI355_ACT_F16 / MI355_ACT_BF16.  A 16-bit cache holds
                          * that dtype (kv_dtype MI355_KV_FP16 <-> F16, MI355_KV_BF16 <-> BF16); the INT8 cache pairs with either */
+    int32_t layout;     /* MI355_KV_LAYOUT_*: 0 = native, so a struct built without the field stays native */
 } mi355_kv_layer_t;
 
 /*
@@ -635,6 +650,11 @@ int    mi355_decoder_set_prefill_rope_table(mi355_decoder_t* d, const float* cos
  * mi355_linear_partial + mi355_rope_kv_write_rows_qk_norm (decode, verify rows, prefill): the fused QKV launches are switched off,
  * since each of their blocks / epilogue jobs owns 32 of a head's hd columns and no job sees the whole head. */
 int    mi355_decoder_set_qk_norm(mi355_decoder_t* d, const void* const* q_norm, const void* const* k_norm);
+/* Layout of every layer's KV cache inside a block (MI355_KV_LAYOUT_*, see mi355_kv_layer_t; the default is native): the step driver,
+ * prefill and the captured graphs then write and read the caches in that layout.  Same contract as mi355_decoder_set_qk_norm: once,
+ * before the first step, prefill or capture, otherwise MI355_ERR_ARG; an unknown value, or a non-native layout on an INT8-KV config,
+ * is MI355_ERR_ARG.  The launch plan does not change with it: the same launches, other addresses. */
+int    mi355_decoder_set_kv_layout(mi355_decoder_t* d, int32_t layout);
 
 /* hipGraph: capture one full step for batch B on an internal stream, then replay
  * `nsteps` times back-to-back on `stream` (greedy feedback stays on device). */

@@ -16,10 +16,12 @@ OK, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_WORKSPACE = 0, -1, -2, -3, -4
 W4, W8, W16 = 4, 8, 16
 KV_FP16, KV_INT8, KV_BF16 = 0, 1, 2
 ACT_F16, ACT_BF16 = 0, 1
+KV_LAYOUT_NATIVE, KV_LAYOUT_REF, KV_LAYOUT_REF_VVEC = 0, 1, 2   # mi355_kv_layer_t.layout: intra-block layout of a cache
+KV_LAYOUT_NAMES = {"native": KV_LAYOUT_NATIVE, "ref": KV_LAYOUT_REF, "ref_vvec": KV_LAYOUT_REF_VVEC}
 EPI_NONE, EPI_SILU_MUL, EPI_OUT_F32, EPI_OUT_IMAGE = 0, 1, 2, 4
 PF_QKV, PF_O, PF_GATE_UP, PF_QKV_LATE, PF_O_LATE, PF_TP_COMM, PF_TP_INLAUNCH, PF_QKV_IN_FOLD = 1, 2, 4, 16, 32, 64, 128, 256   # mi355_decoder_set_weight_prefetch mask bits
 HINT_STAGED, HINT_NO_PERSISTENT = 0x100, 0x200
-ABI_VERSION = 3
+ABI_VERSION = 4
 KC_NAMES = ["gemm_quant", "gemm_lmhead", "attn", "rope_kv", "norm", "other", "comm"]
 
 vp, i32, f32, sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
@@ -32,7 +34,7 @@ class Weight(C.Structure):  # mi355_weight_t
 
 class KVLayer(C.Structure):  # mi355_kv_layer_t
     _fields_ = [("kv_base", vp), ("scale_base", vp), ("kv_dtype", i32), ("page", i32),
-                ("nkv", i32), ("hd", i32), ("num_blocks", i32), ("act_dtype", i32)]
+                ("nkv", i32), ("hd", i32), ("num_blocks", i32), ("act_dtype", i32), ("layout", i32)]
 
 
 class FusedNorm(C.Structure):  # mi355_fused_norm_t
@@ -156,6 +158,7 @@ SIGNATURES = {
     "mi355_decoder_prefill": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
     "mi355_decoder_set_prefill_rope_table": (i32, [vp, vp]),
     "mi355_decoder_set_qk_norm": (i32, [vp, C.POINTER(vp), C.POINTER(vp)]),
+    "mi355_decoder_set_kv_layout": (i32, [vp, i32]),
     "mi355_decoder_capture": (i32, [vp, i32]),
     "mi355_decoder_replay": (i32, [vp, i32, i32, vp]),
     "mi355_decoder_profile": (i32, [vp, i32, i32, C.POINTER(f32), C.POINTER(i32), vp]),

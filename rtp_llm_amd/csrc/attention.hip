@@ -82,8 +82,13 @@ __device__ __forceinline__ f16x8 widen_kv8(uint32_t lo, uint32_t hi) {
 // BF: Q, a 16-bit cache and the output are bf16 (kv_dtype MI355_KV_BF16): bf16 MFMAs for S = K q^T and O = V^T P, P rounded to
 // bf16.  The INT8 cache serves both activation dtypes: its bytes are widened to fp16 (widen_kv8, bias 1152) or to bf16
 // (widen_u8_bf16, bias 128).
-template <int HD, bool INT8, int NT, int NW, int NG, bool BF = false>
+// LAY: MI355_KV_LAYOUT_* of a 16-bit cache (mi355_kv_layer_t).  The fragments are the same in every layout, only where a lane's 16-byte
+// pieces come from differs (load_group); the native value compiles to the kernel without the parameter.
+template <int HD, bool INT8, int NT, int NW, int NG, bool BF = false, int LAY = MI355_KV_LAYOUT_NATIVE>
 __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p) {
+    static_assert(LAY == MI355_KV_LAYOUT_NATIVE || !INT8, "the reference layouts are 16-bit caches");
+    constexpr bool KREF = LAY != MI355_KV_LAYOUT_NATIVE;       // K as [hd/8][page][8]: a lane's piece is one 8-channel chunk of one token
+    constexpr bool VVEC = LAY == MI355_KV_LAYOUT_REF_VVEC;     // V as [page/8][hd][8]: a lane's piece is one channel of one 8-token window
     constexpr float KVB = BF ? 128.f : 1152.f;     // INT8: what a widened cache byte carries on top of its code (see widen_kv8 / _bf16)
     constexpr int NTHR = 64 * NW, GS = 32 * NW;    // threads; tokens one round of the block's waves covers
     constexpr int NSTEP = HD / 32; // QK k-steps
@@ -225,18 +230,25 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
             // head's elements 32; with `long` operands the scalar unit ran a 64 x 64 multiply chain per window (~40 instructions)
             const uint32_t hk = (uint32_t)blk * (uint32_t)(2 * p.nkv) + (uint32_t)kh;
             const uint64_t kbase = (uint64_t)hk * (uint64_t)(uint32_t)head_elems;
-            kof[a] = (long)(kbase + (uint32_t)(ti * HD));
-            vof[a] = (long)(kbase + v_off + (uint32_t)ti);
+            kof[a] = (long)(kbase + (uint32_t)(ti * (KREF ? 8 : HD)));
+            vof[a] = (long)(kbase + v_off + (uint32_t)(VVEC ? ti * HD : ti));   // ti % 8 == 0: window ti / 8 of [page/8][hd][8] starts at ti * hd
             sof[a] = (int)(hk * (uint32_t)p.page) + ti;
         }
         long kb = kof[0]; kb = k1 ? kof[1] : kb; kb = k2 ? kof[2] : kb; kb = k3 ? kof[3] : kb;
         long vb = vof[0]; vb = v1 ? vof[1] : vb; vb = v2 ? vof[2] : vb; vb = v3 ? vof[3] : vb;
         // K: tile tau row j -> token (j & 3) + 4 tau of window j >> 2
-        const char* kl = kvb + (kb + (long)((j & 3) * HD)) * ES + (INT8 ? w * 16 : w * 16);
+        // reference K: k-step s of the lane is chunk 4 s + w, a run of page x 16 bytes per chunk -- four consecutive tokens of one chunk are
+        // the 64 contiguous bytes that four consecutive chunks of one token are natively; the k-step stride depends on the page
+        const char* kl = KREF ? kvb + (kb + (long)((j & 3) * 8) + (long)w * p.page * 8) * ES
+                              : kvb + (kb + (long)((j & 3) * HD)) * ES + (INT8 ? w * 16 : w * 16);
+        const long kstep = (long)4 * p.page * 8 * ES;
 #pragma unroll
         for (int tau = 0; tau < 2; ++tau) {
-            const char* krow = kl + tau * 4 * HD * ES;
-            if (INT8) {
+            const char* krow = kl + tau * 4 * (KREF ? 8 : HD) * ES;
+            if constexpr (KREF) {
+#pragma unroll
+                for (int s = 0; s < NSTEP; ++s) g.kf[tau][s] = *reinterpret_cast<const u32x4*>(krow + s * kstep);
+            } else if (INT8) {
 #pragma unroll
                 for (int sp = 0; sp < NSTEP / 2; ++sp) g.kf[tau][sp] = *reinterpret_cast<const u32x4*>(krow + sp * 64);
             } else {
@@ -245,8 +257,9 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
             }
         }
         // V: d-block db row j (channel db*16+j), the 8 tokens of window w
-        const char* vl = kvb + (vb + (long)j * p.page) * ES;
-        const long vstep = (long)16 * p.page * ES;
+        // (vectorised reference V: the window's 8 tokens of a channel are one aligned 16-byte piece, channels 16 bytes apart)
+        const char* vl = kvb + (vb + (long)j * (VVEC ? 8 : p.page)) * ES;
+        const long vstep = (long)16 * (VVEC ? 8 : p.page) * ES;
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
             const char* vrow = vl + db * vstep;
@@ -635,6 +648,7 @@ int launch_attn(const void* q, const mi355_kv_layer_t* kv, const int32_t* block_
                 const int32_t* seq_lens, int32_t seq_lens_minus_one, int32_t B, int32_t q_len, int32_t nh, float scale,
                 int32_t max_seq_len, void* out, void* workspace, size_t workspace_bytes, mi355_stream_t stream, int img_mblk = 0) {
     MI355_CHECK_ARG(q && kv && kv->kv_base && block_table && seq_lens && out, "paged_attn: null pointer");
+    MI355_CHECK_KV_LAYOUT(kv, "paged_attn");
     MI355_CHECK_ARG(kv->hd == 64 || kv->hd == 128, "paged_attn: hd=%d (64 or 128)", kv->hd);
     MI355_CHECK_ARG(kv->page >= 16 && kv->page % 8 == 0, "paged_attn: page=%d (>= 16, multiple of 8)", kv->page);
     MI355_CHECK_ARG(B > 0 && q_len > 0 && nh > 0 && kv->nkv > 0 && nh % kv->nkv == 0 && nh / kv->nkv <= 16,
@@ -684,9 +698,17 @@ int launch_attn(const void* q, const mi355_kv_layer_t* kv, const int32_t* block_
     MI355_CHECK_ARG(int8 || (bf == (kv->kv_dtype == MI355_KV_BF16)), "paged_attn: a 16-bit cache has the dtype of the activations");
 #define LB_(HD_, I8_) do { if (NT == 1) hipLaunchKernelGGL((paged_attn_kernel<HD_, I8_, 1, 4, (I8_ ? 4 : 2), true>), grid, dim3(256), 0, st, p); \
                            else         hipLaunchKernelGGL((paged_attn_kernel<HD_, I8_, 2, 4, 2, true>), grid, dim3(256), 0, st, p); } while (0)
-    if (bf)            { if (kv->hd == 128) { if (int8) LB_(128, true); else LB_(128, false); } else { if (int8) LB_(64, true); else LB_(64, false); } }
+    // a reference layout (16-bit caches only, checked above): the instantiation the native cache of the same shape takes, with the layout's addressing
+#define LR_(LAY_) do { if (bf) { if (kv->hd == 128) LY_(128, true, LAY_); else LY_(64, true, LAY_); } else { if (kv->hd == 128) LY_(128, false, LAY_); else LY_(64, false, LAY_); } } while (0)
+#define LY_(HD_, BF_, LAY_) do { if (NT == 1) hipLaunchKernelGGL((paged_attn_kernel<HD_, false, 1, 4, 2, BF_, LAY_>), grid, dim3(256), 0, st, p); \
+                                 else         hipLaunchKernelGGL((paged_attn_kernel<HD_, false, 2, 4, 2, BF_, LAY_>), grid, dim3(256), 0, st, p); } while (0)
+    if (kv->layout == MI355_KV_LAYOUT_REF)           LR_(MI355_KV_LAYOUT_REF);
+    else if (kv->layout == MI355_KV_LAYOUT_REF_VVEC) LR_(MI355_KV_LAYOUT_REF_VVEC);
+    else if (bf)       { if (kv->hd == 128) { if (int8) LB_(128, true); else LB_(128, false); } else { if (int8) LB_(64, true); else LB_(64, false); } }
     else if (kv->hd == 128) { if (int8) L2_(128, true); else L2_(128, false); }
     else               { if (int8) L2_(64, true);  else L2_(64, false); }
+#undef LY_
+#undef LR_
 #undef LB_
 #undef L2_
 #undef L_

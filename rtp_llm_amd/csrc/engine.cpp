@@ -22,7 +22,8 @@
 //   TP attached, <= tp_fuse_rows                          | qkv_rope_kv_write, or as staged               | linear_partial                      | linear_direct            | linear_partial                      | allreduce_fused
 //   TP, external transport / segment caller               | "                                             | linear_partial                      | linear_direct            | linear_partial                      | add_rmsnorm (fold -> ar_buf) + all-reduce; add_rmsnorm opens the next segment
 // Between QKV and O: paged_attn_rows (+ partition reduce), as paged_attn_rows_img where the O launch reads an image.  Activations are handed over row-major
-// or as fragment-ordered images (common.h act_img_index); no standalone reduce / add / activation kernels.
+// or as fragment-ordered images (common.h act_img_index); no standalone reduce / add / activation kernels.  The KV block layout (mi355_decoder_set_kv_layout)
+// is not a column: every cell that touches a cache takes it through kv_of, which carries the layout -- the same launches, other addresses.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <algorithm>
@@ -117,6 +118,7 @@ struct mi355_decoder {
     // Qwen3 (mi355_decoder_set_qk_norm): per-layer [hd] weights of the per-head Q / K RMSNorm, empty for Qwen2 / Llama.  Set, the QKV
     // half of every layer is split-K + mi355_rope_kv_write_rows_qk_norm: plan_launches takes the fused QKV launches away
     std::vector<const void*> q_norm, k_norm;
+    int    kv_layout; // MI355_KV_LAYOUT_* of every layer's cache (mi355_decoder_set_kv_layout); native unless set
     bool   started;   // a step, prefill or capture has been enqueued: the launch plan is fixed
     // graphs
     hipStream_t                    cap_stream;
@@ -208,6 +210,7 @@ mi355_kv_layer_t kv_of(const mi355_decoder* d, int l) {
     kv.kv_dtype = d->cfg.kv_dtype; kv.page = d->cfg.page; kv.nkv = d->cfg.nkv; kv.hd = d->cfg.hd;
     kv.num_blocks = d->cfg.num_blocks;
     kv.act_dtype = d->cfg.act_dtype;
+    kv.layout = d->kv_layout;
     return kv;
 }
 
@@ -374,6 +377,7 @@ extern "C" mi355_decoder_t* mi355_decoder_create(const mi355_model_config_t* cfg
     carve_all(d, *cfg, bufs->workspace);
     d->xn = bufs->hidden; // the normed hidden state lives in the caller-visible buffer
     d->started = false;
+    d->kv_layout = MI355_KV_LAYOUT_NATIVE;
     d->B = 0; d->q_len = 1; d->cap_stream = nullptr; d->prof_on = false; d->ev_used = 0; d->ar = nullptr; d->vocab_offset = 0;
     d->has_ext = false; d->pairs_local = d->pairs_all = nullptr;
     d->side_stream = nullptr; d->ev_fork = d->ev_join = nullptr; d->overlap = false;
@@ -790,6 +794,21 @@ extern "C" int mi355_decoder_set_qk_norm(mi355_decoder_t* d, const void* const* 
     d->q_norm.assign(q_norm, q_norm + d->cfg.num_layers);
     d->k_norm.assign(k_norm, k_norm + d->cfg.num_layers);
     return plan_launches(d);
+}
+
+// The intra-block layout of the caches (mi355_kv_layer_t.layout): every launch of the step, of prefill and of a captured graph takes its cache through
+// kv_of, so the layout is fixed before the first of them.  No stage selector of the StepPlan depends on it: the same launches, other addresses.
+extern "C" int mi355_decoder_set_kv_layout(mi355_decoder_t* d, int32_t layout) {
+    if (!d) { mi355_set_error("decoder_set_kv_layout: null decoder"); return MI355_ERR_ARG; }
+    if (d->started || !d->graphs.empty()) {
+        mi355_set_error("decoder_set_kv_layout: must be called before the first step, prefill or capture"); return MI355_ERR_ARG;
+    }
+    if (const char* why = mi355_kv_layout_problem(layout, d->cfg.kv_dtype, d->cfg.hd, d->cfg.page)) {
+        mi355_set_error("decoder_set_kv_layout: layout=%d kv_dtype=%d hd=%d page=%d: %s", layout, d->cfg.kv_dtype, d->cfg.hd, d->cfg.page, why);
+        return MI355_ERR_ARG;
+    }
+    d->kv_layout = layout;
+    return MI355_OK;
 }
 
 // ------------------------------------------------------------------ prefill

@@ -935,6 +935,7 @@ extern "C" int mi355_qkv_rope_kv_write(const void* x, int32_t M, const mi355_wei
     MI355_CHECK_ARG(kv && kv->kv_base && cos_sin && positions && block_table && q_out, "qkv_rope_kv_write: null pointer");
     MI355_CHECK_ARG(kv->page > 0 && nh > 0 && kv->nkv > 0 && max_pos > 0 && max_blocks_per_seq > 0 && kv->num_blocks > 0,
                     "qkv_rope_kv_write: bad dims");
+    MI355_CHECK_KV_LAYOUT(kv, "qkv_rope_kv_write");
     if (norm) if (int e = check_fused_norm(norm, M, wqkv->K, "qkv_rope_kv_write")) return e;
     if (M > (norm ? 16 : 64) || !mi355_fullk_weight_ok(wqkv) || rope_dim != kv->hd) return MI355_ERR_UNSUPPORTED;
     GemmParams p; fill_params(p, x, M, wqkv);
@@ -1055,6 +1056,7 @@ extern "C" int mi355_qkv_rope_kv_write_img(const void* x_img, int32_t M, const m
     MI355_CHECK_ARG(kv && kv->kv_base && cos_sin && positions && block_table && q_out, "qkv_rope_kv_write_img: null pointer");
     MI355_CHECK_ARG(kv->page > 0 && nh > 0 && kv->nkv > 0 && max_pos > 0 && max_blocks_per_seq > 0 && kv->num_blocks > 0,
                     "qkv_rope_kv_write_img: bad dims");
+    MI355_CHECK_KV_LAYOUT(kv, "qkv_rope_kv_write_img");
     if (M < 1 || M > 64 || !img_weight_ok(wqkv) || rope_dim != kv->hd) return MI355_ERR_UNSUPPORTED;
     GemmParams p; fill_params(p, x_img, M, wqkv);
     p.mode = MODE_F16; p.bias = (const f16*)qkv_bias; p.ldy = wqkv->N;

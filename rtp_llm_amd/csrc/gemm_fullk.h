@@ -13,6 +13,9 @@ struct RopeEpi {
     int32_t*       oob_count;
     void*          kv_base;
     f16*           q_out;
+    // the cache's intra-block layout (mi355_kv_layer_t.layout) as strides, so that the epilogue is the same code for every layout: inside a head's
+    // page * hd elements, K (tok, d) sits at tok * k_tok + (d / 8) * k_chunk + d % 8 and V (tok, d) at d * v_d + (tok / 8) * v_win + tok % 8
+    int            k_tok, k_chunk, v_d, v_win;
 };
 struct FullKParams {
     GemmParams g;
@@ -52,5 +55,14 @@ struct FullKParams {
 #define FK_STAMP(i) do { } while (0)
 #endif
 enum { FK_PLAIN = 0, FK_RESID = 1, FK_ROPE = 2, FK_PUB = 3 };
+
+inline void set_kv_layout(RopeEpi& r, int layout, int hd, int page) {
+    const bool kref = layout != MI355_KV_LAYOUT_NATIVE, vvec = layout == MI355_KV_LAYOUT_REF_VVEC;
+    r.k_tok = kref ? 8 : hd;   r.k_chunk = kref ? page * 8 : 8;    // [page][hd]  |  [hd/8][page][8]
+    r.v_d   = vvec ? 8 : page; r.v_win   = vvec ? hd * 8 : 8;      // [hd][page]  |  [page/8][hd][8]
+}
+// offset of the epilogue's K piece (4 channels from d0, d0 % 4 == 0: inside one 8-channel chunk, so one 8-byte store in every layout)
+__device__ __forceinline__ int kv_k_offset(const RopeEpi& r, int tok, int d0) { return tok * r.k_tok + (d0 >> 3) * r.k_chunk + (d0 & 7); }
+__device__ __forceinline__ int kv_v_offset(const RopeEpi& r, int tok, int d) { return d * r.v_d + (tok >> 3) * r.v_win + (tok & 7); }
 
 } // namespace

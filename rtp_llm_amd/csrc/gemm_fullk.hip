@@ -481,11 +481,13 @@ __global__ __launch_bounds__(MB >= 3 ? (TPB >= 2 ? 512 : 768) : 1024) void gemm_
         const size_t blk_base   = ((size_t)blk * 2 + (is_v ? 1 : 0)) * R.nkv + kh;
         f16* dst = (f16*)R.kv_base + blk_base * head_elems;
         if (!is_v) {
-            *reinterpret_cast<f16x4*>(dst + tok * R.hd + d0) = o0;
-            *reinterpret_cast<f16x4*>(dst + tok * R.hd + d0 + half) = o1;
+            *reinterpret_cast<f16x4*>(dst + kv_k_offset(R, tok, d0)) = o0;
+            *reinterpret_cast<f16x4*>(dst + kv_k_offset(R, tok, d0 + half)) = o1;
         } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { dst[(d0 + r) * R.page + tok] = o0[r]; dst[(d0 + r + half) * R.page + tok] = o1[r]; }
+            for (int r = 0; r < 4; ++r) {
+                dst[kv_v_offset(R, tok, d0 + r)] = o0[r]; dst[kv_v_offset(R, tok, d0 + r + half)] = o1[r];
+            }
         }
     }
 }
@@ -614,7 +616,7 @@ extern "C" int mi355_gemm_fullk_rope(const void* gp, int wbits, int group_size, 
     RopeEpi& r = fp.r;
     r.cos_sin = cos_sin; r.positions = positions; r.block_table = block_table; r.max_blocks = max_blocks_per_seq;
     r.nh = nh; r.nkv = kv->nkv; r.hd = kv->hd; r.page = kv->page; r.max_pos = max_pos; r.num_blocks = kv->num_blocks;
-    r.q_len = q_len; r.oob_count = oob_count; r.kv_base = kv->kv_base; r.q_out = (f16*)q_out;
+    r.q_len = q_len; r.oob_count = oob_count; r.kv_base = kv->kv_base; r.q_out = (f16*)q_out; set_kv_layout(r, kv->layout, kv->hd, kv->page);
     if (norm) {
         set_norm(fp, (const mi355_fused_norm_t*)norm);
         return launch_fullk<2, FK_ROPE, true>(fp, group_size, nheads * (kv->hd / 32), (hipStream_t)stream);
@@ -662,6 +664,6 @@ extern "C" int mi355_gemm_fullk_rope_img(const void* gp, int wbits, int group_si
     RopeEpi& r = fp.r;
     r.cos_sin = cos_sin; r.positions = positions; r.block_table = block_table; r.max_blocks = max_blocks_per_seq;
     r.nh = nh; r.nkv = kv->nkv; r.hd = kv->hd; r.page = kv->page; r.max_pos = max_pos; r.num_blocks = kv->num_blocks;
-    r.q_len = q_len; r.oob_count = oob_count; r.kv_base = kv->kv_base; r.q_out = (f16*)q_out;
+    r.q_len = q_len; r.oob_count = oob_count; r.kv_base = kv->kv_base; r.q_out = (f16*)q_out; set_kv_layout(r, kv->layout, kv->hd, kv->page);
     return mi355_gemm_fullk64(&fp, FK_ROPE, group_size, stream);
 }

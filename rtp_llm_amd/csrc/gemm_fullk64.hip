@@ -364,11 +364,13 @@ __global__ __launch_bounds__(1024) void gemm_fullk64_kernel(const FullKParams fp
         const size_t blk_base   = ((size_t)blk * 2 + (is_v ? 1 : 0)) * R.nkv + kh;
         f16* dst = (f16*)R.kv_base + blk_base * head_elems;
         if (!is_v) {
-            *reinterpret_cast<f16x4*>(dst + tok * R.hd + d0) = o0;
-            *reinterpret_cast<f16x4*>(dst + tok * R.hd + d0 + half) = o1;
+            *reinterpret_cast<f16x4*>(dst + kv_k_offset(R, tok, d0)) = o0;
+            *reinterpret_cast<f16x4*>(dst + kv_k_offset(R, tok, d0 + half)) = o1;
         } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { dst[(d0 + r) * R.page + tok] = o0[r]; dst[(d0 + r + half) * R.page + tok] = o1[r]; }
+            for (int r = 0; r < 4; ++r) {
+                dst[kv_v_offset(R, tok, d0 + r)] = o0[r]; dst[kv_v_offset(R, tok, d0 + r + half)] = o1[r];
+            }
         }
     }
     }   // epilogue jobs of this wave

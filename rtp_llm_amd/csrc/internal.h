@@ -2,6 +2,23 @@
 // of the public C-ABI (include/mi355_decode.h).
 #pragma once
 #include "../../include/mi355_decode.h"
+/* Why an entry point must refuse this cache's intra-block layout (mi355_kv_layer_t.layout), or NULL: the non-native layouts exist for
+ * the 16-bit caches with hd 64 / 128 and page 16 / 32 / 64 only; every entry point that takes a cache asks before it launches anything. */
+static inline const char* mi355_kv_layout_problem(int32_t layout, int32_t kv_dtype, int32_t hd, int32_t page) {
+    if (layout == MI355_KV_LAYOUT_NATIVE) return 0;
+    if (layout != MI355_KV_LAYOUT_REF && layout != MI355_KV_LAYOUT_REF_VVEC) return "unknown kv layout";
+    if (kv_dtype != MI355_KV_FP16 && kv_dtype != MI355_KV_BF16) return "the reference kv layouts take fp16 / bf16 caches only (no INT8)";
+    if (hd != 64 && hd != 128) return "the reference kv layouts take hd 64 or 128";
+    if (page != 16 && page != 32 && page != 64) return "the reference kv layouts take page 16, 32 or 64";
+    return 0;
+}
+#define MI355_CHECK_KV_LAYOUT(kv, name)                                                                                         \
+    do {                                                                                                                        \
+        if (const char* why__ = mi355_kv_layout_problem((kv)->layout, (kv)->kv_dtype, (kv)->hd, (kv)->page)) {                  \
+            mi355_set_error("%s: layout=%d kv_dtype=%d hd=%d page=%d: %s", name, (kv)->layout, (kv)->kv_dtype, (kv)->hd, (kv)->page, why__); \
+            return MI355_ERR_ARG;                                                                                               \
+        }                                                                                                                       \
+    } while (0)
 #ifdef __cplusplus
 extern "C" {
 #endif

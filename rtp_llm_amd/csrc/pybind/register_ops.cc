@@ -40,6 +40,7 @@ namespace mi355 {
 // ---- mirrors of the data contract (same field names; decode fields only) -------------------------------------------
 struct AttentionConfigs {            // rtp_llm/cpp/model_utils/AttentionConfig.h:24-85 (+ RopeConfig.h:7-42: dim, base)
     int64_t head_num = 0, kv_head_num = 0, size_per_head = 0, tokens_per_block = 16, max_seq_len = 8192;
+    int64_t kv_layout = MI355_KV_LAYOUT_NATIVE;   // intra-block layout of the caches these ops write / read (MI355_KV_LAYOUT_*; not a field of the reference's struct)
     int64_t rope_dim = 0;
     double  rope_base = 10000.0, softmax_extra_scale = 1.0;
     // RopeConfig.h:7-40: style (1 Base, 3 DynamicNTK, 4 QwenDynamicNTK, 5 Yarn, 6 Llama3; linear = Base with scale), scale = HF factor, factor1 / factor2 =
@@ -209,6 +210,7 @@ inline mi355_kv_layer_t kv_of(const AttentionConfigs& c, const LayerKVCache& kv,
     k.hd         = (int)c.size_per_head;
     k.num_blocks = (int)(kv.kv_cache_base.numel() / (2 * c.kv_head_num * k.page * c.size_per_head));
     k.act_dtype  = act;
+    k.layout     = (int32_t)c.kv_layout;   // the C entry points refuse an unknown value and INT8 with a reference layout
     return k;
 }
 
@@ -243,6 +245,7 @@ public:
         return q;
     }
     int64_t oob_count() const { return oob_.defined() ? oob_.item<int32_t>() : 0; }   // synchronises; diagnostics only
+    void set_kv_layout(int64_t layout) { cfg_.kv_layout = layout; }   // an op built from the reference's AttentionConfigs, which has no such field
 
 private:
     AttentionConfigs cfg_;
@@ -276,6 +279,8 @@ public:
               "mi355_paged_decode_attn");
         return out;
     }
+
+    void set_kv_layout(int64_t layout) { cfg_.kv_layout = layout; }
 
 private:
     AttentionConfigs cfg_;
@@ -380,6 +385,7 @@ void registerPyModuleOps(py::module& m) {
         .def_readwrite("kv_head_num", &AttentionConfigs::kv_head_num)
         .def_readwrite("size_per_head", &AttentionConfigs::size_per_head)
         .def_readwrite("tokens_per_block", &AttentionConfigs::tokens_per_block)
+        .def_readwrite("kv_layout", &AttentionConfigs::kv_layout)
         .def_readwrite("max_seq_len", &AttentionConfigs::max_seq_len)
         .def_readwrite("rope_dim", &AttentionConfigs::rope_dim)
         .def_readwrite("rope_base", &AttentionConfigs::rope_base)
@@ -422,14 +428,16 @@ void registerPyModuleOps(py::module& m) {
 #endif
         .def("prepare", &Mi355RopeKVCacheDecodeOp::prepare, py::arg("attn_inputs"))
         .def("forward", &Mi355RopeKVCacheDecodeOp::forward, py::arg("qkv"), py::arg("kv_cache"), py::arg("params"))
-        .def("oob_count", &Mi355RopeKVCacheDecodeOp::oob_count);
+        .def("oob_count", &Mi355RopeKVCacheDecodeOp::oob_count)
+        .def("set_kv_layout", &Mi355RopeKVCacheDecodeOp::set_kv_layout, py::arg("layout"));
     py::class_<Mi355PagedAttnDecodeOp>(m, "Mi355PagedAttnDecodeOp")
         .def(py::init<const AttentionConfigs&>(), py::arg("attn_configs"))
 #ifdef MI355_REFERENCE_TREE
         .def(py::init<const rtp_llm::AttentionConfigs&>(), py::arg("attn_configs"))
 #endif
         .def("prepare", &Mi355PagedAttnDecodeOp::prepare, py::arg("attn_inputs"))
-        .def("forward", &Mi355PagedAttnDecodeOp::forward, py::arg("q"), py::arg("kv_cache"), py::arg("params"));
+        .def("forward", &Mi355PagedAttnDecodeOp::forward, py::arg("q"), py::arg("kv_cache"), py::arg("params"))
+        .def("set_kv_layout", &Mi355PagedAttnDecodeOp::set_kv_layout, py::arg("layout"));
     py::class_<Mi355WeightOnlyLinear>(m, "Mi355WeightOnlyLinear")
         .def(py::init<torch::Tensor, std::optional<torch::Tensor>, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                       std::optional<torch::Tensor>>(),

@@ -16,6 +16,7 @@
 // holds the whole head, so the norm costs one wave_sum: y = w * act(x * rsqrt(sum(x^2) / hd + eps)), fp32 sum of squares,
 // w = q_norm / k_norm [hd] shared by all heads (HF Qwen3RMSNorm, the arithmetic of oracle.rmsnorm); V heads are untouched.
 #include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -32,6 +33,7 @@ struct RopeParams {
     void*          kv_base;
     float*         scale_base;
     int            kv_int8;
+    int            layout;   // MI355_KV_LAYOUT_*: where a (token, channel) lives inside a head's page * hd elements (16-bit caches)
     f16*           q_out;
     const f16*     q_norm;   // QKN only: [hd] weights of the per-head norms
     const f16*     k_norm;
@@ -129,8 +131,13 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(const RopeParams p) 
     const size_t head_elems = (size_t)p.page * p.hd;
     const size_t blk_base   = ((size_t)blk * 2 + (is_v ? 1 : 0)) * p.nkv + kh; // in units of heads
     int s0, s1; // element offsets inside this head's [page*hd] region
-    if (!is_v) { s0 = tok * p.hd + lane; s1 = s0 + half; }
-    else       { s0 = lane * p.page + tok; s1 = (lane + half) * p.page + tok; }
+    if (!is_v) {
+        if (p.layout == MI355_KV_LAYOUT_NATIVE) { s0 = tok * p.hd + lane; s1 = s0 + half; }
+        else { s0 = ((lane >> 3) * p.page + tok) * 8 + (lane & 7); s1 = s0 + half * p.page; }   // [hd/8][page][8]: the pair's chunk sits hd/16 chunks on
+    } else {
+        if (p.layout != MI355_KV_LAYOUT_REF_VVEC) { s0 = lane * p.page + tok; s1 = (lane + half) * p.page + tok; }
+        else { s0 = ((tok >> 3) * p.hd + lane) * 8 + (tok & 7); s1 = s0 + half * 8; }            // [page/8][hd][8]
+    }
     if (!p.kv_int8) {
         if (act) {
             raw16* dst = (raw16*)p.kv_base + blk_base * head_elems;
@@ -171,6 +178,7 @@ int rope_kv_launch(const void* qkv_f16, const float* partials, int32_t nsplit, i
     MI355_CHECK_ARG(q_len >= 1 && T % q_len == 0, "rope_kv_write: T=%d must be a multiple of q_len=%d", T, q_len);
     MI355_CHECK_ARG((qkv_f16 != nullptr) != (partials != nullptr), "rope_kv_write: exactly one of qkv_f16 / partials");
     MI355_CHECK_ARG(kv && kv->kv_base && cos_sin && positions && block_table && q_out, "rope_kv_write: null pointer");
+    MI355_CHECK_KV_LAYOUT(kv, "rope_kv_write");
     MI355_CHECK_ARG(kv->hd == 64 || kv->hd == 128, "rope_kv_write: hd=%d (64 or 128)", kv->hd);
     MI355_CHECK_ARG(rope_dim == kv->hd, "rope_kv_write: rope_dim=%d must equal hd=%d", rope_dim, kv->hd);
     MI355_CHECK_ARG(kv->page > 0 && T > 0 && nh > 0 && kv->nkv > 0 && max_pos > 0 && max_blocks_per_seq > 0 && kv->num_blocks > 0,
@@ -189,7 +197,7 @@ int rope_kv_launch(const void* qkv_f16, const float* partials, int32_t nsplit, i
     p.cos_sin = cos_sin; p.positions = positions; p.block_table = block_table; p.max_blocks = max_blocks_per_seq;
     p.T = T; p.nh = nh; p.nkv = kv->nkv; p.hd = kv->hd; p.page = kv->page; p.kv_base = kv->kv_base;
     p.max_pos = max_pos; p.num_blocks = kv->num_blocks; p.oob_count = oob_count; p.q_len = q_len;
-    p.scale_base = kv->scale_base; p.kv_int8 = kv->kv_dtype == MI355_KV_INT8; p.q_out = (f16*)q_out;
+    p.scale_base = kv->scale_base; p.kv_int8 = kv->kv_dtype == MI355_KV_INT8; p.layout = kv->layout; p.q_out = (f16*)q_out;
     p.q_norm = (const f16*)q_norm; p.k_norm = (const f16*)k_norm; p.eps = eps;
     const dim3 grid(T, cdiv(nheads, 4));
     if (qkn) {

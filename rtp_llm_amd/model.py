@@ -383,9 +383,11 @@ class DenseMLP(nn.Module):
 
 class Qwen2DecoderModel(nn.Module):
     """qwen3.py:82-138 for the Qwen2/Llama family and Qwen3 dense (cfg.qk_norm: layers carry q_norm / k_norm);
-    forward(input_ids, attn_inputs, kv_caches) -> hidden."""
+    forward(input_ids, fmha_impl, kv_caches) -> hidden for every row of input_ids: one token per sequence with a decode impl, the packed
+    prompt tokens of a prefill batch with a prefill impl (prepare_fmha_impl picks by attn_inputs.is_prefill); logits() on the rows
+    the caller selects.  kv_layout: _C.KV_LAYOUT_* of the kv_caches handed to forward (attention.AttentionConfigs.kv_layout)."""
 
-    def __init__(self, cfg: ModelConfig, weights: Dict, page: int, max_seq_len: int):
+    def __init__(self, cfg: ModelConfig, weights: Dict, page: int, max_seq_len: int, kv_layout: int = _C.KV_LAYOUT_NATIVE):
         super().__init__()
         self.cfg, self.page = cfg, page
         dev = weights["embedding"].device
@@ -398,7 +400,7 @@ class Qwen2DecoderModel(nn.Module):
             self.layers.append(m)
         self.norm = RMSNorm(weights["final_norm"], cfg.rms_eps)
         self.lm_head = LinearFactory.create_linear(weights["lm_head"].w)
-        self.attn_cfg = AttentionConfigs(cfg.nh, cfg.nkv, cfg.hd, cfg.hd, cfg.rope_theta, max_seq_len, 1.0, page)
+        self.attn_cfg = AttentionConfigs(cfg.nh, cfg.nkv, cfg.hd, cfg.hd, cfg.rope_theta, max_seq_len, 1.0, page, kv_layout=kv_layout)
         self.cos_sin = rope_table(cfg, dev)
 
     def prepare_fmha_impl(self, attn_inputs: PyAttentionInputs):   # module_base.py:77-109
@@ -424,8 +426,11 @@ class DecoderEngine:
     """Owns the device buffers and drives csrc/engine.cpp.  Greedy decode only (top_k = 1)."""
 
     def __init__(self, cfg: ModelConfig, weights: Dict, *, kv_int8: bool, page: int, num_blocks: int, max_batch: int,
-                 max_seq_len: int, device, tp_size: int = 1, vocab_full: Optional[int] = None, dtype: torch.dtype = torch.float16):
-        """dtype: activation dtype of the step (torch.float16 or torch.bfloat16; the reference runs either).  bf16: every 16-bit
+                 max_seq_len: int, device, tp_size: int = 1, vocab_full: Optional[int] = None, dtype: torch.dtype = torch.float16,
+                 kv_layout: int = _C.KV_LAYOUT_NATIVE):
+        """kv_layout: _C.KV_LAYOUT_* -- the intra-block layout of self.kv (kvcache.py); a reference layout lets the engine decode on
+        top of blocks the reference's ops wrote, and hand its own blocks back.  16-bit caches only.
+        dtype: activation dtype of the step (torch.float16 or torch.bfloat16; the reference runs either).  bf16: every 16-bit
         tensor of the model (embedding, norm weights, biases, a 16-bit lm_head / linear) is converted once here, the KV cache is
         bf16 (or INT8), W4 / W8 weights are shared as they are."""
         if dtype not in (torch.float16, torch.bfloat16):
@@ -498,6 +503,14 @@ class DecoderEngine:
             raise _C.Mi355Error("decoder_create failed: " + self.lib.mi355_last_error().decode())
         if cfg.qk_norm:   # Qwen3: before any step -- the QKV half of every layer becomes split-K + the normalising KV writer
             _C.check(self.lib.mi355_decoder_set_qk_norm(self.handle, qn_ptrs, kn_ptrs), "decoder_set_qk_norm")
+        self.kv_layout = _C.KV_LAYOUT_NATIVE
+        if kv_layout != _C.KV_LAYOUT_NATIVE:
+            self.set_kv_layout(kv_layout)
+
+    def set_kv_layout(self, layout: int):
+        """Before the first step, prefill or capture only; raises on an INT8-KV engine with a reference layout and on an unknown value."""
+        _C.check(self.lib.mi355_decoder_set_kv_layout(self.handle, int(layout)), "decoder_set_kv_layout")
+        self.kv_layout = int(layout)
 
     def __del__(self):
         try:

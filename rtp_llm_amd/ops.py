@@ -48,8 +48,10 @@ def weight_struct(w: PackedWeight, act: torch.dtype = torch.float16) -> _C.Weigh
 
 
 def kv_struct(kv_base: torch.Tensor, scale_base: Optional[torch.Tensor], page: int, nkv: int, hd: int,
-              act: Optional[torch.dtype] = None) -> _C.KVLayer:
-    """act: dtype of the Q / K / V rows that go with this cache (default: the cache's own 16-bit dtype, fp16 for an INT8 cache)."""
+              act: Optional[torch.dtype] = None, *, layout: int = _C.KV_LAYOUT_NATIVE) -> _C.KVLayer:
+    """act: dtype of the Q / K / V rows that go with this cache (default: the cache's own 16-bit dtype, fp16 for an INT8 cache).
+    layout: _C.KV_LAYOUT_* -- how a block of this cache is laid out inside (kvcache.py); the library refuses the reference layouts
+    on an INT8 cache and any unknown value."""
     int8 = kv_base.dtype == torch.int8
     if int8 and scale_base is None:
         raise _C.Mi355Error("int8 KV cache requires the fp32 scale plane")
@@ -59,7 +61,7 @@ def kv_struct(kv_base: torch.Tensor, scale_base: Optional[torch.Tensor], page: i
     if not int8 and act != kv_base.dtype:
         raise _C.Mi355Error(f"a {kv_base.dtype} cache takes {kv_base.dtype} rows, got {act}")
     return _C.KVLayer(kv_base.data_ptr(), 0 if scale_base is None else scale_base.data_ptr(), kvd, page, nkv, hd, nblk,
-                      _C.ACT_BF16 if act == torch.bfloat16 else _C.ACT_F16)
+                      _C.ACT_BF16 if act == torch.bfloat16 else _C.ACT_F16, int(layout))
 
 
 def _act_of_cache(kv_base: torch.Tensor) -> torch.dtype:
@@ -162,13 +164,14 @@ def norm_linear(h: torch.Tensor, norm, w: PackedWeight, bias: Optional[torch.Ten
 
 
 def qkv_rope_kv_write(x: torch.Tensor, wqkv: PackedWeight, qkv_bias, cos_sin, positions, block_table, kv_base, scale_base,
-                      nh: int, nkv: int, hd: int, page: int, q_len: int = 1, oob_count: Optional[torch.Tensor] = None, norm=None):
+                      nh: int, nkv: int, hd: int, page: int, q_len: int = 1, oob_count: Optional[torch.Tensor] = None, norm=None,
+                      *, layout: int = _C.KV_LAYOUT_NATIVE):
     """[RMSNorm +] QKV projection + bias + RoPE + Q extract + fp16 paged KV write in one launch; None when not taken (INT8
     cache, non-W4 weights): compose linear + rope_kv_write_rows then.  norm = (tile_sumsq, weight, eps): x is un-normed."""
     _chk(x, torch.float16, "qkv_rope_kv_write.x"); _chk(positions, torch.int32, "positions"); _chk(block_table, torch.int32, "block_table")
     T = x.numel() // wqkv.K
     q_out = torch.empty(T, nh, hd, dtype=torch.float16, device=x.device)
-    kv = kv_struct(kv_base, scale_base, page, nkv, hd)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, layout=layout)
     ws_struct = weight_struct(wqkv)
     fn = _fused_norm(norm, T, wqkv.K)
     rc = _C.lib().mi355_qkv_rope_kv_write(x.data_ptr(), T, C.byref(ws_struct), _p(qkv_bias), None if fn is None else C.byref(fn),
@@ -223,11 +226,12 @@ def add_rmsnorm_img(x: torch.Tensor, residual: Optional[torch.Tensor], weight: t
 
 
 def paged_attention_rows_img(q: torch.Tensor, kv_base, scale_base, block_table: torch.Tensor, positions: torch.Tensor, nkv: int,
-                             page: int, q_len: int, max_seq_len: int, scale: Optional[float] = None) -> ActImage:
+                             page: int, q_len: int, max_seq_len: int, scale: Optional[float] = None, *,
+                             layout: int = _C.KV_LAYOUT_NATIVE) -> ActImage:
     """paged_attention_rows with the output written as an activation image (<= 64 rows)."""
     _chk_act(q, "paged_attention_rows_img.q"); _chk(block_table, torch.int32, "block_table"); _chk(positions, torch.int32, "positions")
     T, nh, hd = q.shape
-    kv = kv_struct(kv_base, scale_base, page, nkv, hd, q.dtype)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, q.dtype, layout=layout)
     img = _new_image(T, nh * hd, torch.float16, q.device, q.dtype)
     need = _C.lib().mi355_paged_attn_workspace_bytes(T, nh, hd, max_seq_len)
     ws = _workspace(need, q.device)
@@ -371,7 +375,8 @@ def linear_partial_img(x: ActImage, w: PackedWeight, max_splits: int = 16):
 
 
 def qkv_rope_kv_write_img(x: ActImage, wqkv: PackedWeight, qkv_bias, cos_sin, positions, block_table, kv_base, scale_base,
-                          nh: int, nkv: int, hd: int, page: int, q_len: int = 1, oob_count: Optional[torch.Tensor] = None):
+                          nh: int, nkv: int, hd: int, page: int, q_len: int = 1, oob_count: Optional[torch.Tensor] = None,
+                          *, layout: int = _C.KV_LAYOUT_NATIVE):
     """qkv_rope_kv_write for 1-64 rows (the step driver: from 5) with the activations as an image; None when the shape is not taken."""
     _chk(x.data, torch.float16, "qkv_rope_kv_write_img.x"); _chk(positions, torch.int32, "positions"); _chk(block_table, torch.int32, "block_table")
     T = x.M
@@ -379,7 +384,7 @@ def qkv_rope_kv_write_img(x: ActImage, wqkv: PackedWeight, qkv_bias, cos_sin, po
         raise _C.Mi355Error(f"qkv_rope_kv_write_img: image K={x.K} against K={wqkv.K}")
     act = _act_of_cache(kv_base) if kv_base.dtype != torch.int8 else torch.float16    # q / bias / cache share the step's 16-bit dtype
     q_out = torch.empty(T, nh, hd, dtype=act, device=x.data.device)
-    kv = kv_struct(kv_base, scale_base, page, nkv, hd, act)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, act, layout=layout)
     ws_struct = weight_struct(wqkv, act)
     rc = _C.lib().mi355_qkv_rope_kv_write_img(x.data.data_ptr(), T, C.byref(ws_struct), _p(qkv_bias), cos_sin.data_ptr(), hd, cos_sin.shape[0],
                                               positions.data_ptr(), block_table.data_ptr(), block_table.shape[1], q_len, nh,
@@ -575,7 +580,7 @@ def rejection_sample(draft_token_ids: torch.Tensor, target_token_ids: torch.Tens
 # ------------------------------------------------------------------ attention
 def rope_kv_write(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], cos_sin: torch.Tensor, positions: torch.Tensor,
                   block_table: torch.Tensor, kv_base: torch.Tensor, scale_base: Optional[torch.Tensor], nh: int, nkv: int,
-                  hd: int, page: int, oob_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  hd: int, page: int, oob_count: Optional[torch.Tensor] = None, *, layout: int = _C.KV_LAYOUT_NATIVE) -> torch.Tensor:
     """RoPE + bias + Q-extract + paged KV write for decode tokens; returns q [T, nh, hd].  Tokens with a position or
     block id out of range are not written; `oob_count` (int32 [1], device) counts them."""
     _chk_act(qkv, "rope_kv_write.qkv"); _chk(cos_sin, torch.float32, "rope_kv_write.cos_sin")
@@ -584,7 +589,7 @@ def rope_kv_write(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], cos_sin: 
         _chk(qkv_bias, qkv.dtype, "rope_kv_write.qkv_bias")
     T = qkv.shape[0]
     q_out = torch.empty(T, nh, hd, dtype=qkv.dtype, device=qkv.device)
-    kv = kv_struct(kv_base, scale_base, page, nkv, hd, qkv.dtype)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, qkv.dtype, layout=layout)
     _C.check(_C.lib().mi355_rope_kv_write(qkv.data_ptr(), None, 0, qkv.shape[1], _p(qkv_bias), cos_sin.data_ptr(), hd,
                                           cos_sin.shape[0], positions.data_ptr(), block_table.data_ptr(),
                                           block_table.shape[1], T, nh, C.byref(kv), q_out.data_ptr(), _p(oob_count), _stream()),
@@ -593,14 +598,14 @@ def rope_kv_write(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], cos_sin: 
 
 
 def rope_kv_write_rows(qkv: torch.Tensor, qkv_bias, cos_sin, positions, block_table, kv_base, scale_base, nh: int, nkv: int,
-                       hd: int, page: int, q_len: int, oob_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       hd: int, page: int, q_len: int, oob_count: Optional[torch.Tensor] = None, *, layout: int = _C.KV_LAYOUT_NATIVE) -> torch.Tensor:
     """q_len rows per sequence: qkv [B*q_len, ...], positions [B*q_len] (< 0 = padding row), block_table [B, M]."""
     _chk_act(qkv, "rope_kv_write_rows.qkv"); _chk(positions, torch.int32, "positions"); _chk(block_table, torch.int32, "block_table")
     if qkv_bias is not None:
         _chk(qkv_bias, qkv.dtype, "rope_kv_write_rows.qkv_bias")
     T = qkv.shape[0]
     q_out = torch.empty(T, nh, hd, dtype=qkv.dtype, device=qkv.device)
-    kv = kv_struct(kv_base, scale_base, page, nkv, hd, qkv.dtype)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, qkv.dtype, layout=layout)
     _C.check(_C.lib().mi355_rope_kv_write_rows(qkv.data_ptr(), None, 0, qkv.shape[1], _p(qkv_bias), cos_sin.data_ptr(), hd,
                                                cos_sin.shape[0], positions.data_ptr(), block_table.data_ptr(), block_table.shape[1],
                                                T, q_len, nh, C.byref(kv), q_out.data_ptr(), _p(oob_count), _stream()),
@@ -610,7 +615,7 @@ def rope_kv_write_rows(qkv: torch.Tensor, qkv_bias, cos_sin, positions, block_ta
 
 def rope_kv_write_rows_qk_norm(qkv: torch.Tensor, qkv_bias, q_norm: torch.Tensor, k_norm: torch.Tensor, eps: float, cos_sin, positions,
                                block_table, kv_base, scale_base, nh: int, nkv: int, hd: int, page: int, q_len: int = 1,
-                               oob_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+                               oob_count: Optional[torch.Tensor] = None, *, layout: int = _C.KV_LAYOUT_NATIVE) -> torch.Tensor:
     """Qwen3 form of rope_kv_write_rows: per-head RMSNorm of every Q and K head (q_norm / k_norm [hd], shared by the heads) between the
     bias add and the rotation, in the same launch."""
     _chk_act(qkv, "rope_kv_write_rows_qk_norm.qkv"); _chk(positions, torch.int32, "positions"); _chk(block_table, torch.int32, "block_table")
@@ -622,7 +627,7 @@ def rope_kv_write_rows_qk_norm(qkv: torch.Tensor, qkv_bias, q_norm: torch.Tensor
         _chk(qkv_bias, qkv.dtype, "rope_kv_write_rows_qk_norm.qkv_bias")
     T = qkv.shape[0]
     q_out = torch.empty(T, nh, hd, dtype=qkv.dtype, device=qkv.device)
-    kv = kv_struct(kv_base, scale_base, page, nkv, hd, qkv.dtype)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, qkv.dtype, layout=layout)
     _C.check(_C.lib().mi355_rope_kv_write_rows_qk_norm(qkv.data_ptr(), None, 0, qkv.shape[1], _p(qkv_bias), q_norm.data_ptr(),
                                                        k_norm.data_ptr(), eps, cos_sin.data_ptr(), hd, cos_sin.shape[0], positions.data_ptr(),
                                                        block_table.data_ptr(), block_table.shape[1], T, q_len, nh, C.byref(kv),
@@ -632,11 +637,12 @@ def rope_kv_write_rows_qk_norm(qkv: torch.Tensor, qkv_bias, q_norm: torch.Tensor
 
 
 def paged_attention_rows(q: torch.Tensor, kv_base, scale_base, block_table: torch.Tensor, positions: torch.Tensor, nkv: int,
-                         page: int, q_len: int, max_seq_len: int, scale: Optional[float] = None) -> torch.Tensor:
+                         page: int, q_len: int, max_seq_len: int, scale: Optional[float] = None, *,
+                         layout: int = _C.KV_LAYOUT_NATIVE) -> torch.Tensor:
     """q [B*q_len, nh, hd]; row i of sequence b attends tokens 0..positions[b*q_len+i] (causal over the paged cache)."""
     _chk_act(q, "paged_attention_rows.q"); _chk(block_table, torch.int32, "block_table"); _chk(positions, torch.int32, "positions")
     T, nh, hd = q.shape
-    kv = kv_struct(kv_base, scale_base, page, nkv, hd, q.dtype)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, q.dtype, layout=layout)
     out = torch.empty(T, nh * hd, dtype=q.dtype, device=q.device)
     need = _C.lib().mi355_paged_attn_workspace_bytes(T, nh, hd, max_seq_len)
     ws = _workspace(need, q.device)
@@ -648,12 +654,12 @@ def paged_attention_rows(q: torch.Tensor, kv_base, scale_base, block_table: torc
 
 def paged_decode_attention(q: torch.Tensor, kv_base: torch.Tensor, scale_base: Optional[torch.Tensor],
                            block_table: torch.Tensor, seq_lens: torch.Tensor, nkv: int, page: int,
-                           max_seq_len: int, scale: Optional[float] = None) -> torch.Tensor:
+                           max_seq_len: int, scale: Optional[float] = None, *, layout: int = _C.KV_LAYOUT_NATIVE) -> torch.Tensor:
     """q [B, nh, hd] -> out [B, nh*hd]; seq_lens = context length including the new token."""
     _chk_act(q, "paged_decode_attention.q"); _chk(block_table, torch.int32, "block_table")
     _chk(seq_lens, torch.int32, "seq_lens")
     B, nh, hd = q.shape
-    kv = kv_struct(kv_base, scale_base, page, nkv, hd, q.dtype)
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, q.dtype, layout=layout)
     out = torch.empty(B, nh * hd, dtype=q.dtype, device=q.device)
     need = _C.lib().mi355_paged_attn_workspace_bytes(B, nh, hd, max_seq_len)
     ws = _workspace(need, q.device)

@@ -1,4 +1,4 @@
-"""Bind the MI355 linear strategies to the REFERENCE's own plug-in classes.
+"""Bind the MI355 linear strategies and attention impls to the REFERENCE's own plug-in classes.
 
 The reference picks a linear implementation by asking every class registered with its ``LinearFactory`` whether it
 ``can_handle`` the weight dict (rtp_llm/models_py/modules/factory/linear/factory.py:33-145; registration at import time
@@ -9,6 +9,7 @@ runs unchanged.  The reference-side call is one line in impl/rocm/__init__.py (I
 """
 from typing import List
 
+from .attention import Mi355PagedDecodeImpl, Mi355PrefillImpl
 from .linear import STRATEGY_IMPLS
 
 
@@ -31,6 +32,20 @@ def register(ref_linear_factory, ref_linear_base, replace_f16: bool = False) -> 
             ref_linear_factory._strategies[:] = [s for s in ref_linear_factory._strategies
                                                  if not _safe_can_handle(s, probe)]
         ref_linear_factory.register(cls)
+        out.append(cls)
+    return out
+
+
+def register_attention(decode_list: list, prefill_list: list, fmha_base) -> List[type]:
+    """Bind the two attention impls to the reference's FMHA plug-in lists (factory/attention/__init__.py: DECODE_MHA_IMPS /
+    PREFILL_MHA_IMPS, first impl whose support() accepts the inputs wins): subclasses of the reference's FMHAImplBase around
+    Mi355PagedDecodeImpl and Mi355PrefillImpl, inserted at the FRONT of the lists.  Registering both keeps writer and reader of the
+    cache on one side; registering by hand only the decode one requires AttentionConfigs.kv_layout to name the reference's layout
+    (INTEGRATION.md section 1).  Returns [decode class, prefill class]."""
+    out = []
+    for impl, lst in ((Mi355PagedDecodeImpl, decode_list), (Mi355PrefillImpl, prefill_list)):
+        cls = type(impl.__name__, (impl, fmha_base), {"__module__": __name__, "__doc__": impl.__doc__})
+        lst.insert(0, cls)
         out.append(cls)
     return out
 
