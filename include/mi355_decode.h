@@ -449,6 +449,36 @@ int mi355_rejection_sample(const float* draft_probs, const int32_t* draft_token_
                            int32_t batch_size, int32_t num_speculative_tokens, int32_t vocab_size,
                            int32_t draft_probs_point_mass, mi355_stream_t stream);
 
+/* The sampler's non-greedy branch as ONE op that a captured step can hold (csrc/sample_fused.hip): the result of
+ * mi355_apply_penalties(temperature) -> mi355_softmax_rows(T = 1) -> mi355_top_k_top_p_sample on fp32 logit rows, without the
+ * probability rows in between and with every parameter read from device memory when the launches run (nothing is baked in: the host
+ * may rewrite the arrays between replays of a graph that holds the op).
+ *   temperature [rows] or NULL (= 1): logit *= 1 / (T + 1e-6);  softmax in fp32;
+ *   top_k [rows] or NULL: <= 0 or >= V keeps all, ties with the k-th value stay; a row with top_k == 1 is a greedy row: ids[r] is the
+ *     arg-max of the logits, lowest index on ties (mi355_argmax), and probs_out[r] its one-hot row;
+ *   top_p [rows] or NULL: an entry is dropped when the mass before it in descending order (equal values in index order; mass of the
+ *     full-vocabulary softmax, not renormalised after top-k) exceeds top_p; |top_p| < 1e-7 reads as 1;
+ *   the draw is by inverse CDF in index order over the survivors with u[r] = uniform_samples[r], or, with uniform_samples == NULL,
+ *     the Philox4x32-10 output x0 for key (seed[r] low word, seed[r] high word) and counter (draw_positions[r], 0, 0, 0):
+ *     u = (x0 >> 8) * 2^-24 -- a function of (seed, position) alone, whatever the batch and however often a graph has been replayed;
+ *   uniform_out [rows] (nullable) reports u, probs_out [rows][ld_out] (nullable) receives the renormalised survivors.
+ * A row's id and probs_out row are a pure function of that row, its parameters and u: a row is always cut into the same segments and
+ * all sums are integer sums (fixed point, 2^-40), so they do not depend on rows, on the row index or on timing.
+ * workspace: mi355_sample_logits_workspace_bytes(rows, V) bytes, 8-byte aligned; one memset node and nine launches. */
+size_t mi355_sample_logits_workspace_bytes(int32_t rows, int32_t V);
+int mi355_sample_logits(const float* logits, int32_t rows, int32_t V, int32_t ld,
+                        const float* temperature, const int32_t* top_k, const float* top_p,
+                        const float* uniform_samples, const uint64_t* seed, const int32_t* draw_positions,
+                        int32_t* ids, float* uniform_out, float* probs_out, int32_t ld_out,
+                        void* workspace, size_t workspace_bytes, mi355_stream_t stream);
+/* The repetition / presence / frequency arithmetic of mi355_apply_penalties over a row-major device-side history:
+ * history [rows][history_ld] int32, of which row r holds min(history_len[r], history_ld) tokens -- the lengths are read on the device,
+ * so a captured launch follows a growing history.  Ids outside [0, V) are skipped, every seen id is penalised once with its count.
+ * penalty_ws: [rows][V] int32 scratch (zeroed here).  No temperature: mi355_sample_logits applies it. */
+int mi355_apply_penalties_history(float* logits, int32_t rows, int32_t V, int32_t ld, const float* repetition_penalty,
+                                  const float* presence_penalty, const float* frequency_penalty, const int32_t* history,
+                                  int32_t history_ld, const int32_t* history_len, int32_t* penalty_ws, mi355_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Tensor-parallel all-reduce over peer-mapped memory (xGMI) -- replaces the reference's custom one-shot all-reduce
  * TrtllmArFusionHandle (bindings/rocm/TrtllmAllReduceFusion.h:14-55; kernels trtllm_allreduce_fusion.cu:431-540) and,
@@ -655,6 +685,29 @@ int    mi355_decoder_set_qk_norm(mi355_decoder_t* d, const void* const* q_norm, 
  * before the first step, prefill or capture, otherwise MI355_ERR_ARG; an unknown value, or a non-native layout on an INT8-KV config,
  * is MI355_ERR_ARG.  The launch plan does not change with it: the same launches, other addresses. */
 int    mi355_decoder_set_kv_layout(mi355_decoder_t* d, int32_t layout);
+
+/* Sampled decoding inside the step (tp_size == 1): with a sampling config set, the tail of mi355_decoder_finish(d, 1, ...) after
+ * mi355_decoder_begin, of mi355_decoder_step for every B <= max_batch and of what mi355_decoder_capture records becomes
+ *   1. mi355_apply_penalties_history over history / history_len, when any penalty pointer is set: IN PLACE on bufs.logits, which
+ *      then holds the penalised logits;
+ *   2. mi355_sample_logits (temperature, top_k, top_p, Philox draw with seed[b] at draw position positions[b] + 1);
+ *   3. token_ids[b] = id, positions[b] += 1 (as the greedy tail);
+ *   4. history[b][history_len[b]] = id and history_len[b] += 1 while history_len[b] < history_ld (the token is still produced
+ *      once the history is full); skipped without a history.
+ * so that mi355_decoder_replay(nsteps) leaves the tokens of all its steps on the device.  All arrays are device arrays of max_batch
+ * entries (history: [max_batch][history_ld]) owned by the caller, read when the launches run: the host may rewrite them between
+ * steps and replays.  seed is required; temperature / top_k / top_p / the penalties may be NULL; history and history_len are
+ * required with a penalty.  workspace: mi355_decoder_sampling_workspace_bytes(cfg) bytes, 256-byte aligned.  After
+ * mi355_decoder_begin_rows with q_len > 1 (verify rows) the tail stays greedy.  tp_size > 1: MI355_ERR_UNSUPPORTED (the lm_head is
+ * split over the vocabulary).  s == NULL: back to the greedy tail.  Legal whenever no step is in flight; drops captured graphs. */
+typedef struct {
+    const float* temperature; const int32_t* top_k; const float* top_p; const uint64_t* seed;
+    const float* repetition_penalty; const float* presence_penalty; const float* frequency_penalty;
+    int32_t* history; int32_t* history_len; int32_t history_ld;
+    void* workspace; size_t workspace_bytes;
+} mi355_sampling_t;
+size_t mi355_decoder_sampling_workspace_bytes(const mi355_model_config_t* cfg);
+int    mi355_decoder_set_sampling(mi355_decoder_t* d, const mi355_sampling_t* s);
 
 /* hipGraph: capture one full step for batch B on an internal stream, then replay
  * `nsteps` times back-to-back on `stream` (greedy feedback stays on device). */

@@ -69,6 +69,13 @@ ALL_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_voi
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
+class Sampling(C.Structure):
+    """mi355_sampling_t: device arrays of the sampled tail of the step driver (mi355_decoder_set_sampling)."""
+    _fields_ = [("temperature", vp), ("top_k", vp), ("top_p", vp), ("seed", vp),
+                ("repetition_penalty", vp), ("presence_penalty", vp), ("frequency_penalty", vp),
+                ("history", vp), ("history_len", vp), ("history_ld", i32), ("workspace", vp), ("workspace_bytes", sz)]
+
+
 class Collective(C.Structure):
     """mi355_collective_t: an external transport for the TP points of the step (RCCL fallback)."""
     _fields_ = [("ctx", C.c_void_p), ("all_reduce_f16", ALL_REDUCE_FN), ("all_reduce_bf16", ALL_REDUCE_FN), ("all_gather", ALL_GATHER_FN),
@@ -117,6 +124,9 @@ SIGNATURES = {
     "mi355_apply_penalties": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "mi355_ban_repeat_ngram": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, vp]),
     "mi355_top_k_top_p_sample": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
+    "mi355_sample_logits_workspace_bytes": (sz, [i32, i32]),
+    "mi355_sample_logits": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "mi355_apply_penalties_history": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
     "mi355_rejection_sample": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mi355_allreduce_handle_bytes": (sz, []),
     "mi355_allreduce_create": (vp, [i32, i32, sz, vp]),
@@ -159,6 +169,8 @@ SIGNATURES = {
     "mi355_decoder_set_prefill_rope_table": (i32, [vp, vp]),
     "mi355_decoder_set_qk_norm": (i32, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "mi355_decoder_set_kv_layout": (i32, [vp, i32]),
+    "mi355_decoder_sampling_workspace_bytes": (sz, [C.POINTER(ModelConfig)]),
+    "mi355_decoder_set_sampling": (i32, [vp, C.POINTER(Sampling)]),
     "mi355_decoder_capture": (i32, [vp, i32]),
     "mi355_decoder_replay": (i32, [vp, i32, i32, vp]),
     "mi355_decoder_profile": (i32, [vp, i32, i32, C.POINTER(f32), C.POINTER(i32), vp]),

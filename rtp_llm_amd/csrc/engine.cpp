@@ -120,6 +120,12 @@ struct mi355_decoder {
     std::vector<const void*> q_norm, k_norm;
     int    kv_layout; // MI355_KV_LAYOUT_* of every layer's cache (mi355_decoder_set_kv_layout); native unless set
     bool   started;   // a step, prefill or capture has been enqueued: the launch plan is fixed
+    // sampled decoding (mi355_decoder_set_sampling): the tail of a decode step samples instead of taking the arg-max
+    bool             sampling_on;
+    mi355_sampling_t sampling;
+    int32_t*         penalty_ws;   // carved from sampling.workspace: [max_batch][vocab] counts (with penalties), then the fused op's workspace
+    void*            sample_ws;
+    size_t           sample_ws_bytes;
     // graphs
     hipStream_t                    cap_stream;
     std::map<int, hipGraphExec_t>  graphs;
@@ -377,6 +383,7 @@ extern "C" mi355_decoder_t* mi355_decoder_create(const mi355_model_config_t* cfg
     carve_all(d, *cfg, bufs->workspace);
     d->xn = bufs->hidden; // the normed hidden state lives in the caller-visible buffer
     d->started = false;
+    d->sampling_on = false; d->penalty_ws = nullptr; d->sample_ws = nullptr; d->sample_ws_bytes = 0;
     d->kv_layout = MI355_KV_LAYOUT_NATIVE;
     d->B = 0; d->q_len = 1; d->cap_stream = nullptr; d->prof_on = false; d->ev_used = 0; d->ar = nullptr; d->vocab_offset = 0;
     d->has_ext = false; d->pairs_local = d->pairs_all = nullptr;
@@ -947,7 +954,54 @@ int greedy_tail(mi355_decoder* d, int B, hipStream_t st) {
     else RUN(MI355_KC_OTHER, mi355_argmax_ex(d->bufs.logits, B, c.vocab, c.vocab, d->bufs.token_ids, d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
     return MI355_OK;
 }
+// sampled ids of B rows of logits -> token_ids, positions + 1 and the history (mi355_decoder_set_sampling; tp_size == 1).  The
+// penalties act in place: bufs.logits holds the penalised logits afterwards.  The token drawn here sits at position positions + 1.
+int sampled_tail(mi355_decoder* d, int B, hipStream_t st) {
+    const auto& c = d->cfg; const mi355_sampling_t& s = d->sampling;
+    if (s.repetition_penalty || s.presence_penalty || s.frequency_penalty)
+        RUN(MI355_KC_OTHER, mi355_apply_penalties_history(d->bufs.logits, B, c.vocab, c.vocab, s.repetition_penalty, s.presence_penalty,
+                                                          s.frequency_penalty, s.history, s.history_ld, s.history_len, d->penalty_ws, st));
+    RUN(MI355_KC_OTHER, mi355_sample_logits_ex(d->bufs.logits, B, c.vocab, c.vocab, s.temperature, s.top_k, s.top_p, nullptr, s.seed,
+                                               d->bufs.positions, 1, d->bufs.token_ids, nullptr, nullptr, 0, d->sample_ws, d->sample_ws_bytes, st));
+    RUN(MI355_KC_OTHER, mi355_sample_feedback(d->bufs.token_ids, B, d->bufs.positions, s.history, s.history_len, s.history_ld, st));
+    return MI355_OK;
+}
+int step_tail(mi355_decoder* d, int B, int q_len, hipStream_t st) {
+    return d->sampling_on && q_len == 1 ? sampled_tail(d, B, st) : greedy_tail(d, B, st);
+}
+size_t sampling_penalty_bytes(const mi355_model_config_t& c) { return align256((size_t)c.max_batch * c.vocab * sizeof(int32_t)); }
 } // namespace
+
+extern "C" size_t mi355_decoder_sampling_workspace_bytes(const mi355_model_config_t* cfg) {
+    if (!cfg || cfg->max_batch <= 0 || cfg->vocab <= 0) return 0;
+    return sampling_penalty_bytes(*cfg) + align256(mi355_sample_logits_workspace_bytes(cfg->max_batch, cfg->vocab));
+}
+
+extern "C" int mi355_decoder_set_sampling(mi355_decoder_t* d, const mi355_sampling_t* s) {
+    if (!d) { mi355_set_error("decoder_set_sampling: decoder is null"); return MI355_ERR_ARG; }
+    if (!s) { drop_graphs(d); d->sampling_on = false; return MI355_OK; }
+    if (d->cfg.tp_size > 1) {
+        mi355_set_error("decoder_set_sampling: tp_size %d: the lm_head is split over the vocabulary, sampling needs tp_size 1", d->cfg.tp_size);
+        return MI355_ERR_UNSUPPORTED;
+    }
+    if (!s->seed) { mi355_set_error("decoder_set_sampling: seed [max_batch] is null"); return MI355_ERR_ARG; }
+    const bool pen = s->repetition_penalty || s->presence_penalty || s->frequency_penalty;
+    if ((pen || s->history || s->history_len) && (!s->history || !s->history_len || s->history_ld <= 0)) {
+        mi355_set_error("decoder_set_sampling: penalties / a history need history [max_batch][history_ld], history_len [max_batch] and history_ld > 0");
+        return MI355_ERR_ARG;
+    }
+    const size_t need = mi355_decoder_sampling_workspace_bytes(&d->cfg);
+    if (!s->workspace || s->workspace_bytes < need || (reinterpret_cast<uintptr_t>(s->workspace) & 255) != 0) {
+        mi355_set_error("decoder_set_sampling: workspace of %zu bytes (256-byte aligned) needed, %zu given", need, s->workspace ? s->workspace_bytes : (size_t)0);
+        return MI355_ERR_WORKSPACE;
+    }
+    drop_graphs(d);
+    d->sampling = *s; d->sampling_on = true;
+    d->penalty_ws = (int32_t*)s->workspace;
+    d->sample_ws = (char*)s->workspace + sampling_penalty_bytes(d->cfg);
+    d->sample_ws_bytes = need - sampling_penalty_bytes(d->cfg);
+    return MI355_OK;
+}
 
 extern "C" int mi355_decoder_finish(mi355_decoder_t* d, int32_t sample, mi355_stream_t stream) {
     if (!d || d->B <= 0) { mi355_set_error("decoder_finish: no step in flight"); return MI355_ERR_ARG; }
@@ -956,7 +1010,7 @@ extern "C" int mi355_decoder_finish(mi355_decoder_t* d, int32_t sample, mi355_st
     if (int e = pf_join(d, st)) return e;
     if (d->plan.meet == MeetSel::EXT) if (int e = meet_ext_tail(d, st, d->model.final_norm)) return e;
     RUN(MI355_KC_GEMM_LMHEAD, mi355_linear_direct(d->xn, B, &d->model.lm_head, nullptr, d->bufs.logits, MI355_EPI_OUT_F32, nullptr, 0, st));
-    return sample ? greedy_tail(d, B, st) : MI355_OK;
+    return sample ? step_tail(d, B, d->q_len, st) : MI355_OK;
 }
 
 extern "C" int mi355_decoder_step(mi355_decoder_t* d, int32_t B, mi355_stream_t stream) {
@@ -968,7 +1022,7 @@ extern "C" int mi355_decoder_step(mi355_decoder_t* d, int32_t B, mi355_stream_t 
         if (B > d->cfg.max_batch) { mi355_set_error("decoder_step: B=%d > max_batch", B); return MI355_ERR_ARG; }
         const int rc = mi355_decoder_prefill(d, d->bufs.token_ids, d->bufs.positions, d->bufs.block_table, B, 1, d->iota, d->bufs.logits,
                                              d->wide_ws, d->wide_ws_bytes, stream);
-        return rc < 0 ? rc : greedy_tail(d, B, (hipStream_t)stream);
+        return rc < 0 ? rc : step_tail(d, B, 1, (hipStream_t)stream);
     }
     int rc = mi355_decoder_begin(d, B, stream);
     for (int l = 0; rc >= 0 && l < d->cfg.num_layers; ++l) {

@@ -71,6 +71,14 @@ int mi355_argmax_candidates(const float* logits, int32_t B, int32_t V, int32_t l
 int mi355_argmax_pairs(const float* logits, int32_t B, int32_t V, int32_t ld, int32_t vocab_offset, void* pairs_out,
                        void* workspace, size_t workspace_bytes, mi355_stream_t stream);
 int mi355_argmax_pick(const void* pairs_all, int32_t world, int32_t B, int32_t* ids, int32_t* positions, mi355_stream_t stream);
+/* sample_fused.hip: mi355_sample_logits drawing at draw_positions[r] + position_add, and the feedback launch of a sampled step
+ * (positions + 1, ids appended to the history while it has room; history / history_len may be NULL) */
+int mi355_sample_logits_ex(const float* logits, int32_t rows, int32_t V, int32_t ld, const float* temperature, const int32_t* top_k,
+                           const float* top_p, const float* uniform_samples, const uint64_t* seed, const int32_t* draw_positions,
+                           int32_t position_add, int32_t* ids, float* uniform_out, float* probs_out, int32_t ld_out, void* workspace,
+                           size_t workspace_bytes, mi355_stream_t stream);
+int mi355_sample_feedback(const int32_t* ids, int32_t B, int32_t* positions, int32_t* history, int32_t* history_len,
+                          int32_t history_ld, mi355_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

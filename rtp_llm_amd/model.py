@@ -728,6 +728,112 @@ class DecoderEngine:
             raise _C.Mi355Error("generate_sampled: the KV writer dropped out-of-range tokens (corrupt block table?)")
         return torch.stack(out, 1).tolist()
 
+    # ---- sampled decoding inside the step
+    def set_sampling(self, *, top_k=None, top_p=None, temperature=None, repetition_penalty=None, presence_penalty=None,
+                     frequency_penalty=None, seeds=0, history_ld: Optional[int] = None):
+        """Give the step a sampling tail (mi355_decoder_set_sampling, tp = 1): step() / capture() / replay() then draw every token on
+        the device -- penalties over the device-side history, temperature, top-k / top-p, Philox draw with the sequence's seed at the
+        token's position -- and append it to the history.  Scalars or one value per sequence slot (max_batch); None leaves a filter /
+        penalty out.  The engine allocates and owns the device arrays, exposed as `self.sampling` (dict of tensors: temperature,
+        top_k, top_p, seed (int64 holding the 64-bit pattern), the penalties, history [max_batch, history_ld], history_len): the
+        host may rewrite them in place between steps and replays.  Captured graphs are dropped: capture again."""
+        dev, MB = self.device, self.max_batch
+
+        def vec(v, dt):
+            if v is None:
+                return None
+            t = torch.as_tensor(v, dtype=dt).reshape(-1)
+            if t.numel() == 1:
+                t = t.expand(MB)
+            if t.numel() > MB:
+                raise _C.Mi355Error("set_sampling: more values than max_batch")
+            out = torch.zeros(MB, dtype=dt)
+            out[: t.numel()] = t
+            return out.to(dev)
+        arr = dict(temperature=vec(temperature, torch.float32), top_k=vec(top_k, torch.int32), top_p=vec(top_p, torch.float32),
+                   seed=vec(seeds, torch.int64), repetition_penalty=vec(repetition_penalty, torch.float32),
+                   presence_penalty=vec(presence_penalty, torch.float32), frequency_penalty=vec(frequency_penalty, torch.float32))
+        L = int(history_ld if history_ld is not None else self.capacity() + 1)
+        arr["history"] = torch.zeros(MB, L, dtype=torch.int32, device=dev)
+        arr["history_len"] = torch.zeros(MB, dtype=torch.int32, device=dev)
+        ws_bytes = self.lib.mi355_decoder_sampling_workspace_bytes(C.byref(self._structs[0]))
+        arr["workspace"] = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        cfg = _C.Sampling(ptr(arr["temperature"]), ptr(arr["top_k"]), ptr(arr["top_p"]), ptr(arr["seed"]), ptr(arr["repetition_penalty"]),
+                          ptr(arr["presence_penalty"]), ptr(arr["frequency_penalty"]), ptr(arr["history"]), ptr(arr["history_len"]), L,
+                          ptr(arr["workspace"]), ws_bytes)
+        torch.cuda.synchronize()      # no step in flight; the arrays of an earlier config may go
+        _C.check(self.lib.mi355_decoder_set_sampling(self.handle, C.byref(cfg)), "decoder_set_sampling")
+        self.sampling = arr
+        return arr
+
+    def clear_sampling(self):
+        """Back to the greedy tail (mi355_decoder_set_sampling(NULL)); captured graphs are dropped."""
+        torch.cuda.synchronize()
+        _C.check(self.lib.mi355_decoder_set_sampling(self.handle, None), "decoder_set_sampling")
+        self.sampling = None
+
+    def seed_history(self, prompts: List[List[int]]):
+        """history[b] = prompt b, history_len[b] = its length (rows past the batch: empty)."""
+        hist, n = self.sampling["history"], self.sampling["history_len"]
+        if any(len(pr) > hist.shape[1] for pr in prompts):
+            raise _C.Mi355Error("seed_history: a prompt is longer than history_ld")
+        host = torch.zeros(len(prompts), hist.shape[1], dtype=torch.int32)
+        for b, pr in enumerate(prompts):
+            host[b, : len(pr)] = torch.tensor(pr, dtype=torch.int32)
+        hist[: len(prompts)].copy_(host)
+        n.zero_()
+        n[: len(prompts)].copy_(torch.tensor([len(pr) for pr in prompts], dtype=torch.int32))
+
+    def begin_sampled(self, prompts: List[List[int]], block_table, max_new_tokens: int = 1, prefill_chunk: int = 512) -> torch.Tensor:
+        """The start of a sampled request under the config of set_sampling: prefill, history seeded with the prompts, first token drawn
+        from the prefill logits (penalties, then the fused op, at draw position len(prompt)) and fed back like a step does.  Afterwards
+        step() / replay() continue the sequences.  Returns the first tokens (device)."""
+        B = len(prompts)
+        s = self.sampling
+        if s["history"].shape[1] < max(len(pr) for pr in prompts) + max_new_tokens:
+            raise _C.Mi355Error("begin_sampled: the history of the sampling config is too short for this request")
+        lens = torch.tensor([len(pr) for pr in prompts], dtype=torch.int32)
+        logits = self.prefill(prompts, block_table, chunk=prefill_chunk)
+        self.seed_history(prompts)
+        self.set_inputs([0] * B, lens.tolist(), block_table)
+        cut = lambda t: None if t is None else t[:B]
+        if any(s[k] is not None for k in ("repetition_penalty", "presence_penalty", "frequency_penalty")):
+            ops.apply_penalties_history(logits, s["history"][:B].contiguous(), s["history_len"][:B], cut(s["repetition_penalty"]),
+                                        cut(s["presence_penalty"]), cut(s["frequency_penalty"]))
+        first = ops.sample_logits(logits, cut(s["temperature"]), cut(s["top_k"]), cut(s["top_p"]), seed=cut(s["seed"]),
+                                  draw_positions=self.positions[:B])
+        self.token_ids[:B].copy_(first)
+        rows = torch.arange(B, device=self.device)
+        s["history"][rows, s["history_len"][:B].long()] = first
+        s["history_len"][:B] += 1
+        return first
+
+    def generate_sampled_graph(self, prompts: List[List[int]], block_table, max_new_tokens: int, *, top_k=None, top_p=None, temperature=None,
+                               repetition_penalty=None, presence_penalty=None, frequency_penalty=None, seeds=0,
+                               prefill_chunk: int = 512, reuse_sampling: bool = False) -> List[List[int]]:
+        """Sampled generation with every decode step inside the captured graph (tp = 1): prefill, the history seeded with the prompts,
+        the first token drawn from the prefill logits by the same ops under the same position convention (the token at position p of
+        a sequence uses the Philox number of (its seed, p)), then max_new_tokens - 1 replayed steps and ONE read of the history.
+        reuse_sampling: keep the config and the graph of the previous call (the host may have rewritten `self.sampling` in place)."""
+        B = len(prompts)
+        if B > self.max_batch or any(len(pr) < 1 for pr in prompts):
+            raise _C.Mi355Error("generate_sampled_graph: batch exceeds max_batch or empty prompt")
+        self.check_room([len(pr) for pr in prompts], max_new_tokens - 1, block_table, "generate_sampled_graph")
+        if not (reuse_sampling and getattr(self, "sampling", None) is not None):
+            self.set_sampling(top_k=top_k, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty,
+                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, seeds=seeds,
+                              history_ld=max(len(pr) for pr in prompts) + max_new_tokens)
+        self.begin_sampled(prompts, block_table, max_new_tokens, prefill_chunk)
+        if max_new_tokens > 1:
+            self.capture(B)
+            self.replay(B, max_new_tokens - 1)
+        s = self.sampling
+        hist = s["history"][:B].cpu()
+        if self.oob_count():
+            raise _C.Mi355Error("generate_sampled_graph: the KV writer dropped out-of-range tokens (corrupt block table?)")
+        return [hist[b, len(pr): len(pr) + max_new_tokens].tolist() for b, pr in enumerate(prompts)]
+
     def capture(self, B: int):
         _C.check(self.lib.mi355_decoder_capture(self.handle, B), "decoder_capture")
 

@@ -549,6 +549,68 @@ def top_k_top_p_sample(probs: torch.Tensor, top_k: Optional[torch.Tensor], top_p
     return (ids, out) if return_probs else ids
 
 
+def sample_logits(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None, top_k: Optional[torch.Tensor] = None,
+                  top_p: Optional[torch.Tensor] = None, uniform: Optional[torch.Tensor] = None, seed: Optional[torch.Tensor] = None,
+                  draw_positions: Optional[torch.Tensor] = None, return_probs: bool = False, return_uniform: bool = False):
+    """The fused sampling tail (mi355_sample_logits): temperature, fp32 softmax, top-k / top-p filter and the inverse-CDF draw on
+    fp32 logit rows [R, V] (rows may be strided: stride(1) == 1, stride(0) >= V).  The draw uses uniform [R], or, without it, the
+    Philox4x32-10 number of (seed [R] int64 holding the 64-bit pattern, draw_positions [R] int32).  A row with top_k == 1 is the
+    arg-max.  -> ids [R] int32 (, renormalised survivors [R, V]) (, the uniforms used [R])."""
+    if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]) \
+            or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise _C.Mi355Error("sample_logits.logits: fp32 rows [R, V] on the GPU with unit column stride")
+    R, V = logits.shape
+    dev = logits.device
+    ld = logits.stride(0) if R > 1 else max(V, logits.stride(0))
+
+    def vec(t, dt, name):
+        if t is None:
+            return None
+        t = t.to(device=dev, dtype=dt).contiguous()
+        if t.numel() != R:
+            raise _C.Mi355Error(f"sample_logits: {name} needs one value per row")
+        return t
+    temp, k, p = vec(temperature, torch.float32, "temperature"), vec(top_k, torch.int32, "top_k"), vec(top_p, torch.float32, "top_p")
+    u, sd, pos = vec(uniform, torch.float32, "uniform"), vec(seed, torch.int64, "seed"), vec(draw_positions, torch.int32, "draw_positions")
+    if u is None and (sd is None or pos is None):
+        raise _C.Mi355Error("sample_logits: needs uniform, or seed and draw_positions")
+    ids = torch.empty(R, dtype=torch.int32, device=dev)
+    out = torch.empty(R, V, dtype=torch.float32, device=dev) if return_probs else None
+    u_out = torch.empty(R, dtype=torch.float32, device=dev) if return_uniform else None
+    nbytes = _C.lib().mi355_sample_logits_workspace_bytes(R, V)
+    ws = _workspace(nbytes, dev)
+    _C.check(_C.lib().mi355_sample_logits(logits.data_ptr(), R, V, ld, _p(temp), _p(k), _p(p), _p(u), _p(sd), _p(pos), ids.data_ptr(),
+                                          _p(u_out), _p(out), V, ws.data_ptr(), ws.numel(), _stream()), "sample_logits")
+    res = (ids,) + ((out,) if return_probs else ()) + ((u_out,) if return_uniform else ())
+    return res if len(res) > 1 else ids
+
+
+def apply_penalties_history(logits: torch.Tensor, history: torch.Tensor, history_len: torch.Tensor,
+                            repetition_penalty: Optional[torch.Tensor] = None, presence_penalty: Optional[torch.Tensor] = None,
+                            frequency_penalty: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place on fp32 logits [B, V]: the repetition / presence / frequency arithmetic of apply_penalties over a row-major history
+    [B, L] int32 of which row b holds min(history_len[b], L) tokens (lengths read on the device: mi355_apply_penalties_history)."""
+    _chk(logits, torch.float32, "apply_penalties_history.logits"); _chk(history, torch.int32, "apply_penalties_history.history")
+    _chk(history_len, torch.int32, "apply_penalties_history.history_len")
+    B, V = logits.shape
+    dev = logits.device
+    if history.dim() != 2 or history.shape[0] != B or history_len.numel() != B:
+        raise _C.Mi355Error("apply_penalties_history: history must be [B, L] and history_len [B]")
+
+    def vec(t, name):
+        if t is None:
+            return None
+        t = t.to(device=dev, dtype=torch.float32).contiguous()
+        if t.numel() != B:
+            raise _C.Mi355Error(f"apply_penalties_history: {name} needs one value per row")
+        return t
+    rep, pres, freq = vec(repetition_penalty, "repetition_penalty"), vec(presence_penalty, "presence_penalty"), vec(frequency_penalty, "frequency_penalty")
+    ws = torch.empty(B, V, dtype=torch.int32, device=dev) if (rep is not None or pres is not None or freq is not None) else None
+    _C.check(_C.lib().mi355_apply_penalties_history(logits.data_ptr(), B, V, V, _p(rep), _p(pres), _p(freq), history.data_ptr(),
+                                                    history.shape[1], history_len.data_ptr(), _p(ws), _stream()), "apply_penalties_history")
+    return logits
+
+
 def rejection_sample(draft_token_ids: torch.Tensor, target_token_ids: torch.Tensor, target_probs: torch.Tensor,
                      uniform_samples: torch.Tensor, do_sample: torch.Tensor, draft_probs: Optional[torch.Tensor] = None):
     """Chain rejection sampling (bindings/rocm/speculative_sampling/sampling.cu:306): draft_token_ids [B,g] int32,
