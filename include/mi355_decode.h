@@ -479,6 +479,29 @@ int mi355_apply_penalties_history(float* logits, int32_t rows, int32_t V, int32_
                                   const float* presence_penalty, const float* frequency_penalty, const int32_t* history,
                                   int32_t history_ld, const int32_t* history_len, int32_t* penalty_ws, mi355_stream_t stream);
 
+/* Log-probabilities of fp32 logit rows (csrc/logprobs.hip): what a serving front end reports per token (logprobs / top_logprobs,
+ * cum_log_probs) without a [rows][V] softmax and without the logits leaving the device.  Per row r, with x[j] = logits[r][j] * inv_t,
+ * inv_t = 1 / (temperature[r] + 1e-6) in fp32 (temperature == NULL: x = logits) -- the scaled logits mi355_sample_logits draws from --
+ * M = max x, lse = M + log(sum_j exp(x[j] - M)) and lp[j] = x[j] - lse: the FULL-vocabulary log-softmax, whatever top-k / top-p cut a
+ * sampler applies afterwards.  A NaN entry counts as -inf (weight 0, never listed).  A row with no entry above -inf has no
+ * distribution: lse = -inf, its token value is NaN and its top_n slots are all (id -1, value -inf).
+ *   ids [rows] or NULL: token_logprobs[r] = lp[ids[r]]; -inf where that entry is -inf; an id outside [0, V) gives NaN and reads nothing;
+ *   lse_out [rows] (nullable) receives lse;
+ *   top_n in [0, MI355_LOGPROBS_MAX_TOP]: top_ids / top_logprobs [rows][top_ld] receive the top_n largest entries with x > -inf,
+ *     descending, equal values in index order (lower index first); slots beyond those (V < top_n, -inf entries): id -1, value -inf.
+ *     Columns [top_n, top_ld) are not written.  The value listed for index j and the token value of id j are the same fp32 number.
+ * A row's outputs are a pure function of the row, its temperature and its id: the row is always cut into the same 32 segments and
+ * every reduction has a fixed order, so they do not depend on rows, on the row index, on ld or on timing.
+ * Everything is read from device memory when the launches run.  workspace: mi355_logprobs_workspace_bytes(rows, V, top_n) bytes
+ * (independent of V), 8-byte aligned; two launches, no memset node, no atomics.  rows == 0: nothing to do. */
+#define MI355_LOGPROBS_MAX_TOP 32
+size_t mi355_logprobs_workspace_bytes(int32_t rows, int32_t V, int32_t top_n);
+int mi355_logprobs(const float* logits, int32_t rows, int32_t V, int32_t ld,
+                   const float* temperature, const int32_t* ids,
+                   int32_t top_n, float* token_logprobs, float* lse_out,
+                   int32_t* top_ids, float* top_logprobs, int32_t top_ld,
+                   void* workspace, size_t workspace_bytes, mi355_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Tensor-parallel all-reduce over peer-mapped memory (xGMI) -- replaces the reference's custom one-shot all-reduce
  * TrtllmArFusionHandle (bindings/rocm/TrtllmAllReduceFusion.h:14-55; kernels trtllm_allreduce_fusion.cu:431-540) and,
@@ -708,6 +731,35 @@ typedef struct {
 } mi355_sampling_t;
 size_t mi355_decoder_sampling_workspace_bytes(const mi355_model_config_t* cfg);
 int    mi355_decoder_set_sampling(mi355_decoder_t* d, const mi355_sampling_t* s);
+
+/* Log-probabilities inside the step (tp_size == 1): with a config set, the tail of every decode step (q_len == 1; eager, captured
+ * or replayed) runs the two launches of mi355_logprobs on bufs.logits behind the choice of the token --
+ *   greedy tail:  arg-max, then the log-probabilities of the unscaled logits (temperature NULL);
+ *   sampled tail: penalties, mi355_sample_logits, then the log-probabilities under the sampling config's temperature of the
+ *                 PENALISED logits (the penalties act in place), then the feedback launch.  A top_k == 1 row is scored under the
+ *                 temperature-scaled distribution like every other row
+ * -- and records them per sequence slot b, at column c = count[b]:
+ *   while c < log_ld: token_logprobs[b][c] = the token's value, top_ids / top_logprobs[b][c][0 .. top_n) = the alternatives
+ *     (mi355_logprobs' order and padding), count[b] = c + 1; once full nothing more is written and count[b] stays;
+ *   cum_log_probs[b] += the token's value at every step regardless (one fp32 add per step), when the pointer is set.
+ * All arrays are device arrays owned by the caller and read when the launches run: the host may rewrite count / cum_log_probs
+ * between steps and replays of the same graph (count = 0 records from column 0 again).  top_n in [0, MI355_LOGPROBS_MAX_TOP];
+ * top_ids / top_logprobs are required with top_n > 0; token_logprobs, count and log_ld >= 1 always.  workspace:
+ * mi355_decoder_logprobs_workspace_bytes(cfg, top_n) bytes, 256-byte aligned.  Independent of mi355_decoder_set_sampling, in either
+ * order.  Verify rows (mi355_decoder_begin_rows with q_len > 1) record nothing.  tp_size > 1: MI355_ERR_UNSUPPORTED (the lm_head is
+ * split over the vocabulary).  lp == NULL: off -- the step is launch for launch what it is without the feature.  Legal whenever no
+ * step is in flight; drops captured graphs. */
+typedef struct {
+    int32_t  top_n, log_ld;           /* alternatives per token; steps recorded per slot */
+    float*   cum_log_probs;           /* [max_batch], += the token's log-probability every step; nullable */
+    float*   token_logprobs;          /* [max_batch][log_ld] */
+    int32_t* top_ids;                 /* [max_batch][log_ld][top_n], with top_n > 0 */
+    float*   top_logprobs;            /* same shape */
+    int32_t* count;                   /* [max_batch]: column the next step writes */
+    void* workspace; size_t workspace_bytes;
+} mi355_logprobs_t;
+size_t mi355_decoder_logprobs_workspace_bytes(const mi355_model_config_t* cfg, int32_t top_n);
+int    mi355_decoder_set_logprobs(mi355_decoder_t* d, const mi355_logprobs_t* lp);
 
 /* hipGraph: capture one full step for batch B on an internal stream, then replay
  * `nsteps` times back-to-back on `stream` (greedy feedback stays on device). */

@@ -22,6 +22,7 @@ EPI_NONE, EPI_SILU_MUL, EPI_OUT_F32, EPI_OUT_IMAGE = 0, 1, 2, 4
 PF_QKV, PF_O, PF_GATE_UP, PF_QKV_LATE, PF_O_LATE, PF_TP_COMM, PF_TP_INLAUNCH, PF_QKV_IN_FOLD = 1, 2, 4, 16, 32, 64, 128, 256   # mi355_decoder_set_weight_prefetch mask bits
 HINT_STAGED, HINT_NO_PERSISTENT = 0x100, 0x200
 ABI_VERSION = 4
+LOGPROBS_MAX_TOP = 32
 KC_NAMES = ["gemm_quant", "gemm_lmhead", "attn", "rope_kv", "norm", "other", "comm"]
 
 vp, i32, f32, sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
@@ -76,6 +77,12 @@ class Sampling(C.Structure):
                 ("history", vp), ("history_len", vp), ("history_ld", i32), ("workspace", vp), ("workspace_bytes", sz)]
 
 
+class Logprobs(C.Structure):
+    """mi355_logprobs_t: the per-slot log-probability recorder of the step driver (mi355_decoder_set_logprobs)."""
+    _fields_ = [("top_n", i32), ("log_ld", i32), ("cum_log_probs", vp), ("token_logprobs", vp), ("top_ids", vp), ("top_logprobs", vp),
+                ("count", vp), ("workspace", vp), ("workspace_bytes", sz)]
+
+
 class Collective(C.Structure):
     """mi355_collective_t: an external transport for the TP points of the step (RCCL fallback)."""
     _fields_ = [("ctx", C.c_void_p), ("all_reduce_f16", ALL_REDUCE_FN), ("all_reduce_bf16", ALL_REDUCE_FN), ("all_gather", ALL_GATHER_FN),
@@ -127,6 +134,8 @@ SIGNATURES = {
     "mi355_sample_logits_workspace_bytes": (sz, [i32, i32]),
     "mi355_sample_logits": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
     "mi355_apply_penalties_history": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
+    "mi355_logprobs_workspace_bytes": (sz, [i32, i32, i32]),
+    "mi355_logprobs": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, sz, vp]),
     "mi355_rejection_sample": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mi355_allreduce_handle_bytes": (sz, []),
     "mi355_allreduce_create": (vp, [i32, i32, sz, vp]),
@@ -171,6 +180,8 @@ SIGNATURES = {
     "mi355_decoder_set_kv_layout": (i32, [vp, i32]),
     "mi355_decoder_sampling_workspace_bytes": (sz, [C.POINTER(ModelConfig)]),
     "mi355_decoder_set_sampling": (i32, [vp, C.POINTER(Sampling)]),
+    "mi355_decoder_logprobs_workspace_bytes": (sz, [C.POINTER(ModelConfig), i32]),
+    "mi355_decoder_set_logprobs": (i32, [vp, C.POINTER(Logprobs)]),
     "mi355_decoder_capture": (i32, [vp, i32]),
     "mi355_decoder_replay": (i32, [vp, i32, i32, vp]),
     "mi355_decoder_profile": (i32, [vp, i32, i32, C.POINTER(f32), C.POINTER(i32), vp]),

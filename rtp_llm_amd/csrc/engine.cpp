@@ -126,6 +126,9 @@ struct mi355_decoder {
     int32_t*         penalty_ws;   // carved from sampling.workspace: [max_batch][vocab] counts (with penalties), then the fused op's workspace
     void*            sample_ws;
     size_t           sample_ws_bytes;
+    // log-probabilities of the chosen tokens (mi355_decoder_set_logprobs): two more launches behind the choice, recorded per slot
+    bool             logprobs_on;
+    mi355_logprobs_t logprobs;
     // graphs
     hipStream_t                    cap_stream;
     std::map<int, hipGraphExec_t>  graphs;
@@ -384,6 +387,7 @@ extern "C" mi355_decoder_t* mi355_decoder_create(const mi355_model_config_t* cfg
     d->xn = bufs->hidden; // the normed hidden state lives in the caller-visible buffer
     d->started = false;
     d->sampling_on = false; d->penalty_ws = nullptr; d->sample_ws = nullptr; d->sample_ws_bytes = 0;
+    d->logprobs_on = false;
     d->kv_layout = MI355_KV_LAYOUT_NATIVE;
     d->B = 0; d->q_len = 1; d->cap_stream = nullptr; d->prof_on = false; d->ev_used = 0; d->ar = nullptr; d->vocab_offset = 0;
     d->has_ext = false; d->pairs_local = d->pairs_all = nullptr;
@@ -944,15 +948,26 @@ int ext_argmax(mi355_decoder* d, int B, hipStream_t st) {
     RUN(MI355_KC_OTHER, mi355_argmax_pick(d->pairs_all, d->ext.world, B, d->bufs.token_ids, d->bufs.positions, st));
     return MI355_OK;
 }
+// log-probabilities of the ids in token_ids under the logits in bufs.logits, recorded per slot (mi355_decoder_set_logprobs): the two
+// launches of logprobs.hip, nothing without a config or on verify rows
+int logprob_tail(mi355_decoder* d, int B, int q_len, const float* temperature, hipStream_t st) {
+    if (!d->logprobs_on || q_len != 1) return MI355_OK;
+    const auto& c = d->cfg; const mi355_logprobs_t& lp = d->logprobs;
+    RUN(MI355_KC_OTHER, mi355_logprobs_segments(d->bufs.logits, B, c.vocab, c.vocab, temperature, lp.top_n, lp.workspace, lp.workspace_bytes, st));
+    RUN(MI355_KC_OTHER, mi355_logprobs_rows(d->bufs.logits, B, c.vocab, c.vocab, temperature, d->bufs.token_ids, lp.top_n, lp.token_logprobs, nullptr,
+                                            lp.top_ids, lp.top_logprobs, lp.top_n, lp.log_ld, lp.count, lp.cum_log_probs, lp.workspace,
+                                            lp.workspace_bytes, st));
+    return MI355_OK;
+}
 // greedy ids of B rows of logits -> token_ids (and positions + 1) for the next step
-int greedy_tail(mi355_decoder* d, int B, hipStream_t st) {
+int greedy_tail(mi355_decoder* d, int B, int q_len, hipStream_t st) {
     const auto& c = d->cfg;
     if (d->ar)   // vocab-split lm_head: (max, index) pairs cross the ranks, not the logits
         RUN(MI355_KC_COMM, mi355_allreduce_argmax(d->ar, d->bufs.logits, B, c.vocab, c.vocab, d->vocab_offset, d->bufs.token_ids,
                                                   d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
     else if (d->has_ext) return ext_argmax(d, B, st);
     else RUN(MI355_KC_OTHER, mi355_argmax_ex(d->bufs.logits, B, c.vocab, c.vocab, d->bufs.token_ids, d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
-    return MI355_OK;
+    return logprob_tail(d, B, q_len, nullptr, st);
 }
 // sampled ids of B rows of logits -> token_ids, positions + 1 and the history (mi355_decoder_set_sampling; tp_size == 1).  The
 // penalties act in place: bufs.logits holds the penalised logits afterwards.  The token drawn here sits at position positions + 1.
@@ -963,11 +978,12 @@ int sampled_tail(mi355_decoder* d, int B, hipStream_t st) {
                                                           s.frequency_penalty, s.history, s.history_ld, s.history_len, d->penalty_ws, st));
     RUN(MI355_KC_OTHER, mi355_sample_logits_ex(d->bufs.logits, B, c.vocab, c.vocab, s.temperature, s.top_k, s.top_p, nullptr, s.seed,
                                                d->bufs.positions, 1, d->bufs.token_ids, nullptr, nullptr, 0, d->sample_ws, d->sample_ws_bytes, st));
+    if (int e = logprob_tail(d, B, 1, s.temperature, st)) return e;
     RUN(MI355_KC_OTHER, mi355_sample_feedback(d->bufs.token_ids, B, d->bufs.positions, s.history, s.history_len, s.history_ld, st));
     return MI355_OK;
 }
 int step_tail(mi355_decoder* d, int B, int q_len, hipStream_t st) {
-    return d->sampling_on && q_len == 1 ? sampled_tail(d, B, st) : greedy_tail(d, B, st);
+    return d->sampling_on && q_len == 1 ? sampled_tail(d, B, st) : greedy_tail(d, B, q_len, st);
 }
 size_t sampling_penalty_bytes(const mi355_model_config_t& c) { return align256((size_t)c.max_batch * c.vocab * sizeof(int32_t)); }
 } // namespace
@@ -1000,6 +1016,38 @@ extern "C" int mi355_decoder_set_sampling(mi355_decoder_t* d, const mi355_sampli
     d->penalty_ws = (int32_t*)s->workspace;
     d->sample_ws = (char*)s->workspace + sampling_penalty_bytes(d->cfg);
     d->sample_ws_bytes = need - sampling_penalty_bytes(d->cfg);
+    return MI355_OK;
+}
+
+extern "C" size_t mi355_decoder_logprobs_workspace_bytes(const mi355_model_config_t* cfg, int32_t top_n) {
+    if (!cfg || cfg->max_batch <= 0 || cfg->vocab <= 0) return 0;
+    return align256(mi355_logprobs_workspace_bytes(cfg->max_batch, cfg->vocab, top_n));
+}
+
+extern "C" int mi355_decoder_set_logprobs(mi355_decoder_t* d, const mi355_logprobs_t* lp) {
+    if (!d) { mi355_set_error("decoder_set_logprobs: decoder is null"); return MI355_ERR_ARG; }
+    if (!lp) { drop_graphs(d); d->logprobs_on = false; return MI355_OK; }
+    if (d->cfg.tp_size > 1) {
+        mi355_set_error("decoder_set_logprobs: tp_size %d: the lm_head is split over the vocabulary, log-probabilities need tp_size 1", d->cfg.tp_size);
+        return MI355_ERR_UNSUPPORTED;
+    }
+    if (lp->top_n < 0 || lp->top_n > MI355_LOGPROBS_MAX_TOP) {
+        mi355_set_error("decoder_set_logprobs: top_n %d outside [0, %d]", lp->top_n, MI355_LOGPROBS_MAX_TOP); return MI355_ERR_ARG;
+    }
+    if (lp->log_ld < 1 || !lp->token_logprobs || !lp->count) {
+        mi355_set_error("decoder_set_logprobs: needs log_ld >= 1 (%d given), token_logprobs [max_batch][log_ld] and count [max_batch]", lp->log_ld);
+        return MI355_ERR_ARG;
+    }
+    if (lp->top_n > 0 && (!lp->top_ids || !lp->top_logprobs)) {
+        mi355_set_error("decoder_set_logprobs: top_n %d needs top_ids and top_logprobs [max_batch][log_ld][top_n]", lp->top_n); return MI355_ERR_ARG;
+    }
+    const size_t need = mi355_decoder_logprobs_workspace_bytes(&d->cfg, lp->top_n);
+    if (!lp->workspace || lp->workspace_bytes < need || (reinterpret_cast<uintptr_t>(lp->workspace) & 255) != 0) {
+        mi355_set_error("decoder_set_logprobs: workspace of %zu bytes (256-byte aligned) needed, %zu given", need, lp->workspace ? lp->workspace_bytes : (size_t)0);
+        return MI355_ERR_WORKSPACE;
+    }
+    drop_graphs(d);
+    d->logprobs = *lp; d->logprobs_on = true;
     return MI355_OK;
 }
 

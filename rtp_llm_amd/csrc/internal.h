@@ -79,6 +79,16 @@ int mi355_sample_logits_ex(const float* logits, int32_t rows, int32_t V, int32_t
                            size_t workspace_bytes, mi355_stream_t stream);
 int mi355_sample_feedback(const int32_t* ids, int32_t B, int32_t* positions, int32_t* history, int32_t* history_len,
                           int32_t history_ld, mi355_stream_t stream);
+/* logprobs.hip: the two launches of mi355_logprobs one by one (the step driver runs and profiles them as two ops).  _rows also takes the
+ * recorder of mi355_decoder_set_logprobs: with count != NULL row r writes column count[r] of token_logprobs [rows][log_ld] and of
+ * top_ids / top_logprobs [rows][log_ld][top_ld] while count[r] < log_ld and then advances it; cum_log_probs[r] (nullable) += the
+ * token's value either way.  count == NULL, log_ld = 1: the public op. */
+int mi355_logprobs_segments(const float* logits, int32_t rows, int32_t V, int32_t ld, const float* temperature, int32_t top_n,
+                            void* workspace, size_t workspace_bytes, mi355_stream_t stream);
+int mi355_logprobs_rows(const float* logits, int32_t rows, int32_t V, int32_t ld, const float* temperature, const int32_t* ids,
+                        int32_t top_n, float* token_logprobs, float* lse_out, int32_t* top_ids, float* top_logprobs, int32_t top_ld,
+                        int32_t log_ld, int32_t* count, float* cum_log_probs, void* workspace, size_t workspace_bytes,
+                        mi355_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

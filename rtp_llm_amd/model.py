@@ -503,6 +503,7 @@ class DecoderEngine:
             raise _C.Mi355Error("decoder_create failed: " + self.lib.mi355_last_error().decode())
         if cfg.qk_norm:   # Qwen3: before any step -- the QKV half of every layer becomes split-K + the normalising KV writer
             _C.check(self.lib.mi355_decoder_set_qk_norm(self.handle, qn_ptrs, kn_ptrs), "decoder_set_qk_norm")
+        self.logprobs = None          # set_logprobs
         self.kv_layout = _C.KV_LAYOUT_NATIVE
         if kv_layout != _C.KV_LAYOUT_NATIVE:
             self.set_kv_layout(kv_layout)
@@ -665,7 +666,10 @@ class DecoderEngine:
         if B > self.max_batch or any(len(pr) < 1 for pr in prompts):
             raise _C.Mi355Error("generate: batch exceeds max_batch or empty prompt")
         self.check_room([len(pr) for pr in prompts], max_new_tokens - 1, block_table, "generate")
-        first = ops.argmax(self.prefill(prompts, block_table, chunk=prefill_chunk))
+        logits = self.prefill(prompts, block_table, chunk=prefill_chunk)
+        first = ops.argmax(logits)
+        if self.logprobs is not None:   # set_logprobs: the first token's record, as the steps write theirs
+            self.record_first_logprobs(logits, first)
         out = [first.clone()]
         self.set_inputs([0] * B, [len(pr) for pr in prompts], block_table)
         self.token_ids[:B].copy_(first)
@@ -773,6 +777,65 @@ class DecoderEngine:
         _C.check(self.lib.mi355_decoder_set_sampling(self.handle, None), "decoder_set_sampling")
         self.sampling = None
 
+    # ---- log-probabilities inside the step
+    def set_logprobs(self, top_n: int = 0, log_ld: Optional[int] = None):
+        """Record the log-probability of every token the step chooses (mi355_decoder_set_logprobs, tp = 1), greedy or sampled, eager or
+        replayed: per sequence slot the token's value and the `top_n` alternatives (<= _C.LOGPROBS_MAX_TOP) of up to `log_ld` steps
+        (default: the engine's capacity) and the running sum -- under the full-vocabulary softmax of the logits the token was chosen
+        from (penalised and temperature-scaled under a sampling config).  The engine allocates and owns the device arrays, exposed as
+        `self.logprobs` (dict: token_logprobs [max_batch, log_ld], top_ids / top_logprobs [max_batch, log_ld, top_n], cum_log_probs
+        [max_batch], count [max_batch] = the column the next step writes): the host may rewrite count / cum_log_probs in place between
+        steps and replays.  Independent of set_sampling, in either order.  Captured graphs are dropped: capture again."""
+        dev, MB = self.device, self.max_batch
+        top_n = int(top_n)
+        L = int(log_ld if log_ld is not None else self.capacity())
+        arr = dict(top_n=top_n, log_ld=L,
+                   token_logprobs=torch.zeros(MB, max(L, 0), dtype=torch.float32, device=dev),
+                   top_ids=torch.full((MB, max(L, 0), max(top_n, 0)), -1, dtype=torch.int32, device=dev),
+                   top_logprobs=torch.full((MB, max(L, 0), max(top_n, 0)), float("-inf"), dtype=torch.float32, device=dev),
+                   cum_log_probs=torch.zeros(MB, dtype=torch.float32, device=dev), count=torch.zeros(MB, dtype=torch.int32, device=dev))
+        ws_bytes = self.lib.mi355_decoder_logprobs_workspace_bytes(C.byref(self._structs[0]), top_n)
+        arr["workspace"] = torch.zeros(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        cfg = _C.Logprobs(top_n, L, ptr(arr["cum_log_probs"]), ptr(arr["token_logprobs"]), ptr(arr["top_ids"]), ptr(arr["top_logprobs"]),
+                          ptr(arr["count"]), ptr(arr["workspace"]), ws_bytes)
+        torch.cuda.synchronize()      # no step in flight; the arrays of an earlier config may go
+        _C.check(self.lib.mi355_decoder_set_logprobs(self.handle, C.byref(cfg)), "decoder_set_logprobs")
+        self.logprobs = arr
+        return arr
+
+    def clear_logprobs(self):
+        """No log-probabilities (mi355_decoder_set_logprobs(NULL)): the step is launch for launch what it was; captured graphs are dropped."""
+        torch.cuda.synchronize()
+        _C.check(self.lib.mi355_decoder_set_logprobs(self.handle, None), "decoder_set_logprobs")
+        self.logprobs = None
+
+    def record_first_logprobs(self, logits: torch.Tensor, ids: torch.Tensor, temperature: Optional[torch.Tensor] = None):
+        """Column 0 of the recorder from the logits a request's first token was chosen from (the prefill logits, after the penalties):
+        the same op a step runs, count = 1 and the running sum started for the B leading slots; the others are left alone."""
+        lp = self.logprobs
+        B, n = logits.shape[0], lp["top_n"]
+        r = ops.logprobs(logits, ids=ids, temperature=temperature, top_n=n)
+        lp["token_logprobs"][:B, 0].copy_(r["token_logprobs"])
+        if n > 0:
+            lp["top_ids"][:B, 0].copy_(r["top_ids"]); lp["top_logprobs"][:B, 0].copy_(r["top_logprobs"])
+        lp["cum_log_probs"][:B].copy_(r["token_logprobs"])
+        lp["count"][:B].fill_(1)
+
+    def read_logprobs(self, B: int, steps: int) -> Dict:
+        """One read-back of the first `steps` recorded columns of the B leading slots (host tensors): the four arrays are packed
+        into one device buffer of 32-bit words, which crosses in a single copy with a single synchronisation."""
+        lp = self.logprobs
+        parts = [("token_logprobs", lp["token_logprobs"][:B, :steps]), ("top_ids", lp["top_ids"][:B, :steps]),
+                 ("top_logprobs", lp["top_logprobs"][:B, :steps]), ("cum_log_probs", lp["cum_log_probs"][:B])]
+        host = torch.cat([t.reshape(-1).view(torch.int32) if t.dtype == torch.float32 else t.reshape(-1) for _, t in parts]).cpu()
+        out, at = {}, 0
+        for name, t in parts:
+            w = host[at: at + t.numel()]
+            out[name] = (w.view(torch.float32) if t.dtype == torch.float32 else w).reshape(t.shape).clone()
+            at += t.numel()
+        return out
+
     def seed_history(self, prompts: List[List[int]]):
         """history[b] = prompt b, history_len[b] = its length (rows past the batch: empty)."""
         hist, n = self.sampling["history"], self.sampling["history_len"]
@@ -804,6 +867,8 @@ class DecoderEngine:
         first = ops.sample_logits(logits, cut(s["temperature"]), cut(s["top_k"]), cut(s["top_p"]), seed=cut(s["seed"]),
                                   draw_positions=self.positions[:B])
         self.token_ids[:B].copy_(first)
+        if self.logprobs is not None:   # what a step records, from the logits the first token was drawn from
+            self.record_first_logprobs(logits, first, cut(s["temperature"]))
         rows = torch.arange(B, device=self.device)
         s["history"][rows, s["history_len"][:B].long()] = first
         s["history_len"][:B] += 1
@@ -811,11 +876,14 @@ class DecoderEngine:
 
     def generate_sampled_graph(self, prompts: List[List[int]], block_table, max_new_tokens: int, *, top_k=None, top_p=None, temperature=None,
                                repetition_penalty=None, presence_penalty=None, frequency_penalty=None, seeds=0,
-                               prefill_chunk: int = 512, reuse_sampling: bool = False) -> List[List[int]]:
+                               prefill_chunk: int = 512, reuse_sampling: bool = False, top_logprobs: Optional[int] = None):
         """Sampled generation with every decode step inside the captured graph (tp = 1): prefill, the history seeded with the prompts,
         the first token drawn from the prefill logits by the same ops under the same position convention (the token at position p of
         a sequence uses the Philox number of (its seed, p)), then max_new_tokens - 1 replayed steps and ONE read of the history.
-        reuse_sampling: keep the config and the graph of the previous call (the host may have rewritten `self.sampling` in place)."""
+        reuse_sampling: keep the config and the graph of the previous call (the host may have rewritten `self.sampling` in place).
+        top_logprobs: None returns the tokens; an int n >= 0 records the log-probabilities inside the same graph (set_logprobs(n))
+        and returns (tokens, {"token_logprobs" [B, T], "top_ids" / "top_logprobs" [B, T, n], "cum_log_probs" [B]}) from one read-back
+        at the end."""
         B = len(prompts)
         if B > self.max_batch or any(len(pr) < 1 for pr in prompts):
             raise _C.Mi355Error("generate_sampled_graph: batch exceeds max_batch or empty prompt")
@@ -824,6 +892,10 @@ class DecoderEngine:
             self.set_sampling(top_k=top_k, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty,
                               presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, seeds=seeds,
                               history_ld=max(len(pr) for pr in prompts) + max_new_tokens)
+        if top_logprobs is not None:
+            lp = self.logprobs
+            if not (reuse_sampling and lp is not None and lp["top_n"] == int(top_logprobs) and lp["log_ld"] >= max_new_tokens):
+                self.set_logprobs(int(top_logprobs), max_new_tokens)
         self.begin_sampled(prompts, block_table, max_new_tokens, prefill_chunk)
         if max_new_tokens > 1:
             self.capture(B)
@@ -832,7 +904,8 @@ class DecoderEngine:
         hist = s["history"][:B].cpu()
         if self.oob_count():
             raise _C.Mi355Error("generate_sampled_graph: the KV writer dropped out-of-range tokens (corrupt block table?)")
-        return [hist[b, len(pr): len(pr) + max_new_tokens].tolist() for b, pr in enumerate(prompts)]
+        toks = [hist[b, len(pr): len(pr) + max_new_tokens].tolist() for b, pr in enumerate(prompts)]
+        return toks if top_logprobs is None else (toks, self.read_logprobs(B, max_new_tokens))
 
     def capture(self, B: int):
         _C.check(self.lib.mi355_decoder_capture(self.handle, B), "decoder_capture")

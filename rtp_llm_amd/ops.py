@@ -585,6 +585,40 @@ def sample_logits(logits: torch.Tensor, temperature: Optional[torch.Tensor] = No
     return res if len(res) > 1 else ids
 
 
+def logprobs(logits: torch.Tensor, ids: Optional[torch.Tensor] = None, temperature: Optional[torch.Tensor] = None, top_n: int = 0):
+    """Log-probabilities under the full-vocabulary softmax of the scaled fp32 logit rows [R, V] (mi355_logprobs; rows may be strided:
+    stride(1) == 1, stride(0) >= V; temperature [R] as in sample_logits).  -> dict: "lse" [R]; with ids [R] "token_logprobs" [R]
+    (NaN for an id outside the row); with top_n > 0 "top_ids" [R, top_n] int32 and "top_logprobs" [R, top_n], descending, equal
+    values by ascending index, padded with id -1 / -inf."""
+    if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]) \
+            or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise _C.Mi355Error("logprobs.logits: fp32 rows [R, V] on the GPU with unit column stride")
+    R, V = logits.shape
+    dev = logits.device
+    ld = logits.stride(0) if R > 1 else max(V, logits.stride(0))
+
+    def vec(t, dt, name):
+        if t is None:
+            return None
+        t = t.to(device=dev, dtype=dt).contiguous()
+        if t.numel() != R:
+            raise _C.Mi355Error(f"logprobs: {name} needs one value per row")
+        return t
+    temp, tok = vec(temperature, torch.float32, "temperature"), vec(ids, torch.int32, "ids")
+    top_n = int(top_n)
+    res = {"lse": torch.empty(R, dtype=torch.float32, device=dev)}
+    if tok is not None:
+        res["token_logprobs"] = torch.empty(R, dtype=torch.float32, device=dev)
+    if top_n > 0:
+        res["top_ids"] = torch.empty(R, top_n, dtype=torch.int32, device=dev)
+        res["top_logprobs"] = torch.empty(R, top_n, dtype=torch.float32, device=dev)
+    nbytes = _C.lib().mi355_logprobs_workspace_bytes(R, V, top_n)
+    ws = _workspace(nbytes, dev)
+    _C.check(_C.lib().mi355_logprobs(logits.data_ptr(), R, V, ld, _p(temp), _p(tok), top_n, _p(res.get("token_logprobs")), res["lse"].data_ptr(),
+                                     _p(res.get("top_ids")), _p(res.get("top_logprobs")), top_n, ws.data_ptr(), ws.numel(), _stream()), "logprobs")
+    return res
+
+
 def apply_penalties_history(logits: torch.Tensor, history: torch.Tensor, history_len: torch.Tensor,
                             repetition_penalty: Optional[torch.Tensor] = None, presence_penalty: Optional[torch.Tensor] = None,
                             frequency_penalty: Optional[torch.Tensor] = None) -> torch.Tensor:

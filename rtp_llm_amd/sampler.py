@@ -12,7 +12,9 @@ and the same host-side shortcuts:
 
 Randomness is explicit: where the reference consumes `generator` inside torch.multinomial, the caller passes one uniform in
 [0, 1) per row (`uniform`), so a run is reproducible and checkable against the oracle.  `cum_log_probs` / `output_log_probs`
-are not on this path (the reference's ROCm branch does not update them per token either)."""
+are not on this host-side path (the reference's ROCm branch does not update them per token either): they are recorded inside the
+step by `DecoderEngine.set_logprobs` (mi355_decoder_set_logprobs; `generate_sampled_graph(..., top_logprobs=n)`), and
+`ops.logprobs` gives them for any fp32 logit rows."""
 from dataclasses import dataclass
 from typing import Optional
 

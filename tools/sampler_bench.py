@@ -5,7 +5,8 @@
     sampler_bench.py --tail     the fused sampling tail (mi355_sample_logits) against the chain temperature + softmax_rows +
                                 top_k_top_p_sample, both replayed from a graph (device time, no host wrapper), alternating
     sampler_bench.py --step     ms / step of the Qwen2-7B W4A16 decode step (b = 64, ctx 1024, graph replay): greedy tail against the
-                                sampled tail, and the host-side generate_sampled loop next to them
+                                sampled tail, each without and with the log-probability recorder (top 0 / top 20), and the
+                                host-side generate_sampled loop next to them
 """
 import argparse
 import os
@@ -83,6 +84,12 @@ def bench_tail(B, V, L):
               f"chain / fused {c[0] / f[0]:5.2f}   same ids: {same}")
     survivors = int((ops.sample_logits(flat, temp, None, p90, uniform=u, return_probs=True)[1][0] > 0).sum())
     print(f"# survivors of row 0 in the flat p = 0.9 setting: {survivors}")
+    # the two launches of mi355_logprobs on the same rows (what a step with the recorder adds to its tail)
+    ids = torch.randint(0, V, (B,), generator=g, dtype=torch.int32).to(dev)
+    r = alternate([(f"top {n}", graphed(lambda n=n: ops.logprobs(peaked, ids=ids, temperature=temp, top_n=n))) for n in (0, 1, 20, 32)])
+    print(f"# mi355_logprobs, B = {B} rows x V = {V} fp32 (graph replay, us per call: median [min .. max] of 7 windows x 30)")
+    for name, t in r.items():
+        print(f"logprobs {name:43s} {t[0]:7.1f} [{t[1]:6.1f} .. {t[2]:6.1f}]")
 
 
 def bench_step(B, ctx, steps):
@@ -112,6 +119,8 @@ def bench_step(B, ctx, steps):
         if getattr(eng, "sampling", None) is not None:
             eng.sampling["history"][:, :ctx].copy_(hist0)
             eng.sampling["history_len"].fill_(ctx)
+        if eng.logprobs is not None:
+            eng.logprobs["count"].zero_()                      # every timed step records
 
     def replay_ms():
         reset(); eng.capture(B); eng.replay(B, 8); torch.cuda.synchronize()
@@ -121,18 +130,33 @@ def bench_step(B, ctx, steps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(); eng.replay(B, steps); e1.record(); torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1) / steps)
-        return sorted(ts)
-    print(f"# decode step, Qwen2-7B W4A16, fp16 KV, b = {B}, ctx {ctx}, graph replay of {steps} steps (ms / step: median [min .. max] of 5 windows)")
-    rows = [("greedy tail", None), ("sampled tail: T 0.7, k 20, p 0.8", dict(temperature=0.7, top_k=20, top_p=0.8)),
-            ("sampled tail: + repetition penalty 1.05", dict(temperature=0.7, top_k=20, top_p=0.8, repetition_penalty=1.05)),
-            ("greedy tail (again)", None)]
-    for name, kw in rows:
-        if kw is None:
-            eng.clear_sampling()
-        else:
-            eng.set_sampling(seeds=torch.arange(B, dtype=torch.int64) + 11, history_ld=max_seq + 1, **kw)
-        t = replay_ms()
-        print(f"{name:48s} {t[2]:7.3f} [{t[0]:7.3f} .. {t[4]:7.3f}] ms / step")
+        return ts
+    passes = 2
+    print(f"# decode step, Qwen2-7B W4A16, fp16 KV, b = {B}, ctx {ctx}, graph replay of {steps} steps "
+          f"(ms / step: median [min .. max] of {5 * passes} windows, the rows taken in turn {passes} times; earlier forms of this "
+          f"mode took 5 windows per row in one pass and repeated the greedy row: their lines do not compare with these one to one)")
+    sampled = dict(temperature=0.7, top_k=20, top_p=0.8)
+    rows = [("greedy tail", None, None), ("greedy tail + logprobs top 0", None, 0), ("greedy tail + logprobs top 20", None, 20),
+            ("sampled tail: T 0.7, k 20, p 0.8", sampled, None), ("sampled tail + logprobs top 0", sampled, 0),
+            ("sampled tail + logprobs top 20", sampled, 20),
+            ("sampled tail: + repetition penalty 1.05", dict(sampled, repetition_penalty=1.05), None),
+            ("sampled tail: + repetition penalty 1.05 + logprobs top 20", dict(sampled, repetition_penalty=1.05), 20)]
+    res = {name: [] for name, _, _ in rows}
+    for _ in range(passes):
+        for name, kw, top in rows:
+            if kw is None:
+                eng.clear_sampling()
+            else:
+                eng.set_sampling(seeds=torch.arange(B, dtype=torch.int64) + 11, history_ld=max_seq + 1, **kw)
+            if top is None:
+                eng.clear_logprobs()
+            else:
+                eng.set_logprobs(top, steps + 8)
+            res[name] += replay_ms()
+    for name, _, _ in rows:
+        t = sorted(res[name])
+        print(f"{name:58s} {t[len(t) // 2]:7.3f} [{t[0]:7.3f} .. {t[-1]:7.3f}] ms / step")
+    eng.clear_logprobs()
     # the host-side path of generate_sampled: one eager step without sampling, sampler.sample_greedy over its logits, ids.cpu()
     from rtp_llm_amd import sampler
     eng.clear_sampling()
