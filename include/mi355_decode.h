@@ -315,6 +315,22 @@ int mi355_paged_attn_rows_img(const void* q, const mi355_kv_layer_t* kv, const i
                               int32_t max_blocks_per_seq, const int32_t* positions, int32_t B, int32_t q_len, int32_t nh,
                               float scale, int32_t max_seq_len, void* out_img, void* workspace, size_t workspace_bytes,
                               mi355_stream_t stream);
+/* Decode attention (q_len = 1, B <= 64 sequences) that takes the step's QKV projection as fp32 split-K slabs [nslab][B][n_pad]
+ * (mi355_linear_partial_img, or mi355_linear_partial on row-major rows) instead of a q tensor; out_img as mi355_paged_attn_rows_img.
+ * The prologue of every (partition, kv head, sequence) block sums the slabs of its G = nh / nkv query heads in index order, adds
+ * qkv_bias (nullable) and rotates -- formula and roundings of mi355_rope_kv_write -- while its first K/V requests are in flight.
+ * The block of the partition that holds positions[b] does the same for the row's k and v head, stores them in the cache for later
+ * steps (K row-major, V channel-major; range checks and *oob_count as mi355_rope_kv_write; a negative position is a padding row:
+ * zero output, nothing stored) and attends to them from registers: the cache walk covers tokens [0, positions[b]), nothing the
+ * launch stores is read back by it.  So the pair (mi355_qkv_rope_kv_write_img, mi355_paged_attn_rows_img) becomes (split-K
+ * launch, this): no q tensor, no writer launch.  16-bit caches (of the activation dtype) in the native block layout with
+ * rope_dim == hd and q_len == 1; an INT8 cache, a reference layout, q_len > 1 or B > 64: MI355_ERR_UNSUPPORTED, nothing launched.
+ * Reference boundary: modules/hybrid/causal_attention.py:75-93 (qkv_proj -> rope / kv write -> attention). */
+int mi355_paged_attn_qkv_slabs_img(const float* slabs, int32_t nslab, int32_t n_pad, const void* qkv_bias, const float* cos_sin,
+                                   int32_t rope_dim, int32_t max_pos, const mi355_kv_layer_t* kv, const int32_t* block_table,
+                                   int32_t max_blocks_per_seq, const int32_t* positions, int32_t B, int32_t q_len, int32_t nh,
+                                   float scale, int32_t max_seq_len, void* out_img, void* workspace, size_t workspace_bytes,
+                                   int32_t* oob_count, mi355_stream_t stream);
 int mi355_linear_residual_img(const void* x_img, int32_t M, const mi355_weight_t* w, const void* bias, const void* residual_in,
                               void* residual_out, float* tile_sumsq_out, int32_t tile_sumsq_ld, mi355_stream_t stream);
 /* mi355_linear_residual_img that also leaves the deferred-norm operands of the rows it produces: xg_img_out = image of
@@ -847,6 +863,14 @@ int mi355_decoder_profile(mi355_decoder_t* d, int32_t B, int32_t nsteps, float* 
 /* Number of tokens the step driver refused to write to the KV cache since creation because their position or block id
  * was out of range (see mi355_rope_kv_write).  Synchronises `stream`.  0 on a healthy run; < 0 = error. */
 int64_t mi355_decoder_oob_count(mi355_decoder_t* d, mi355_stream_t stream);
+
+/* Which QKV launch the step begun last took: 0 = mi355_qkv_rope_kv_write_img, 1 = mi355_qkv_rope_kv_write, 2 = split-K + writer
+ * launch, 3 = split-K slabs folded by mi355_paged_attn_qkv_slabs_img; MI355_ERR_ARG before the first step.  Read-only. */
+int mi355_decoder_qkv_launch(const mi355_decoder_t* d);
+/* Opt in: from `rows` rows on, a decode step (q_len = 1) takes launch 3 above where the configuration allows it (tp 1, W4 group-wise, 16-bit cache in the
+ * native layout, no QK norm).  Off by default (rows <= 0 turns it off again): the path's fp32 sums run in another order, so logits differ from launch 0's in
+ * the last bits.  Measured at Qwen2-7B: slower than launch 0 at 8 rows, equal at 16, faster from 32 -- 17 is the sensible value.  Drops captured steps. */
+int mi355_decoder_set_qkv_slab_rows(mi355_decoder_t* d, int32_t rows);
 
 #ifdef __cplusplus
 }

@@ -120,6 +120,7 @@ SIGNATURES = {
     "mi355_linear_deferred_norm_img": (i32, [vp, i32, C.POINTER(DeferredNorm), C.POINTER(Weight), vp, vp, i32, vp]),
     "mi355_linear_direct_img": (i32, [vp, i32, C.POINTER(Weight), vp, vp, i32, vp]),
     "mi355_linear_partial_img": (i32, [vp, i32, C.POINTER(Weight), vp, i32, vp]),
+    "mi355_paged_attn_qkv_slabs_img": (i32, [vp, i32, i32, vp, vp, i32, i32, C.POINTER(KVLayer), vp, i32, vp, i32, i32, i32, f32, i32, vp, vp, sz, vp, vp]),
     "mi355_qkv_rope_kv_write_img": (i32, [vp, i32, C.POINTER(Weight), vp, vp, i32, i32, vp, vp, i32, i32, i32, C.POINTER(KVLayer), vp, vp, vp]),
     "mi355_qkv_rope_kv_write": (i32, [vp, i32, C.POINTER(Weight), vp, C.POINTER(FusedNorm), vp, i32, i32, vp, vp, i32, i32, i32, C.POINTER(KVLayer), vp, vp, vp]),
     "mi355_paged_attn_workspace_bytes": (sz, [i32, i32, i32, i32]),
@@ -186,6 +187,8 @@ SIGNATURES = {
     "mi355_decoder_replay": (i32, [vp, i32, i32, vp]),
     "mi355_decoder_profile": (i32, [vp, i32, i32, C.POINTER(f32), C.POINTER(i32), vp]),
     "mi355_decoder_oob_count": (C.c_int64, [vp, vp]),
+    "mi355_decoder_qkv_launch": (i32, [vp]),
+    "mi355_decoder_set_qkv_slab_rows": (i32, [vp, i32]),
 }
 
 _lib = None

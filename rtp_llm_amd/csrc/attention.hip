@@ -47,6 +47,13 @@ struct AttnParams {
     uint32_t page_magic;   // 2^32 / page + 1: floor(t / page) == (t * magic) >> 32 for t * page < 2^32
     float scale_log2; // softmax scale * log2(e)
     int img_mblk;     // > 0: out is an activation image of that many row blocks (common.h act_img_index) instead of [rows][nh * hd]
+    // QS instances (mi355_paged_attn_qkv_slabs_img): q, and the new token's k / v, come from the QKV GEMM's split-K slabs
+    const float*   slabs;      // [nslab][B][n_pad] fp32
+    int            nslab, n_pad;
+    const f16*     bias;       // [(nh + 2 nkv) * hd] or null
+    const float*   cos_sin;    // [max_pos][hd / 2][2]
+    int            max_pos;
+    int32_t*       oob_count;  // new tokens refused by the cache write (stale position / block id), or null
 #ifdef MI355_TUNING
     unsigned long long* stamps;   // tools/attn_stamps.py: wall_clock64 per wave at entry / first requests out / first group computed / loop done / merged / exit
 #endif
@@ -62,6 +69,26 @@ __device__ __forceinline__ size_t out_index(const AttnParams& p, int row, int co
 }
 
 constexpr float NEG_BIG = -1e30f;
+
+// The lane combines of common.h (xor16_* / xor32_*) for this kernel, as plain `asm` instead of `asm volatile`.  An `asm volatile` statement counts
+// as a possible store: with one inside the walk's loop hipcc no longer proves the block table unclobbered there and turns the loop's block-id lookups
+// (lookup below) from scalar into VECTOR loads -- the very thing the comment at `Wins` rules out: their vmcnt waits drain every K/V request issued
+// before them, so a wave has no group in flight while it computes.  The statements have no side effect (two registers in, the same two out; the
+// s_nop pads the operand hazard as in common.h), so they need not be volatile; same instructions, same results.
+__device__ __forceinline__ void at_swap16(float v, float& r0, float& r1) {
+    float a = v, b = v;
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    r0 = a; r1 = b;
+}
+__device__ __forceinline__ void at_swap32(float v, float& r0, float& r1) {
+    float a = v, b = v;
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    r0 = a; r1 = b;
+}
+__device__ __forceinline__ float at_xor16_max(float v) { float a, b; at_swap16(v, a, b); return fmaxf(a, b); }
+__device__ __forceinline__ float at_xor32_max(float v) { float a, b; at_swap32(v, a, b); return fmaxf(a, b); }
+__device__ __forceinline__ float at_xor16_sum(float v) { float a, b; at_swap16(v, a, b); return a + b; }
+__device__ __forceinline__ float at_xor32_sum(float v) { float a, b; at_swap32(v, a, b); return a + b; }
 
 // NW waves per block split the partition between them (each wave keeps two 32-token groups of K/V in flight).  NW = 8 for
 // the one-block-per-CU grids (B * nkv * P <= 256) was measured and lost: 34.2 vs 29.8 us at b = 64 / ctx 1024 fp16 KV and
@@ -84,9 +111,16 @@ __device__ __forceinline__ f16x8 widen_kv8(uint32_t lo, uint32_t hi) {
 // (widen_u8_bf16, bias 128).
 // LAY: MI355_KV_LAYOUT_* of a 16-bit cache (mi355_kv_layer_t).  The fragments are the same in every layout, only where a lane's 16-byte
 // pieces come from differs (load_group); the native value compiles to the kernel without the parameter.
-template <int HD, bool INT8, int NT, int NW, int NG, bool BF = false, int LAY = MI355_KV_LAYOUT_NATIVE>
+// QS: decode rows (q_len = 1) whose QKV projection arrives as fp32 split-K slabs.  There is no q tensor and the cache does not hold the
+// row's own token yet: the block folds the slabs of ITS heads (the G query heads of its kv head; in the partition that holds
+// `position` also the k and v head), adds the bias, rotates (the arithmetic and roundings of rope_kv.hip) and hands q to its waves
+// through LDS -- requested ahead of the first K/V group, computed while that group is in flight.  The cache walk covers tokens
+// [0, position); the new token's k / v are stored for later steps and enter THIS step as a last one-token group built from the same
+// rounded 16-bit values in registers: nothing this launch stores is read back by it.  false compiles to the kernel without it.
+template <int HD, bool INT8, int NT, int NW, int NG, bool BF = false, int LAY = MI355_KV_LAYOUT_NATIVE, bool QS = false>
 __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p) {
     static_assert(LAY == MI355_KV_LAYOUT_NATIVE || !INT8, "the reference layouts are 16-bit caches");
+    static_assert(!QS || (!INT8 && NT == 1 && NW == 4 && NG == 2 && LAY == MI355_KV_LAYOUT_NATIVE), "slab prologue: 16-bit native cache, one row per sequence");
     constexpr bool KREF = LAY != MI355_KV_LAYOUT_NATIVE;       // K as [hd/8][page][8]: a lane's piece is one 8-channel chunk of one token
     constexpr bool VVEC = LAY == MI355_KV_LAYOUT_REF_VVEC;     // V as [page/8][hd][8]: a lane's piece is one channel of one 8-token window
     constexpr float KVB = BF ? 128.f : 1152.f;     // INT8: what a widened cache byte carries on top of its code (see widen_kv8 / _bf16)
@@ -118,7 +152,11 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
     }
     int seq_len = 0;
     for (int i = 0; i < nrows; ++i) seq_len = max(seq_len, min(p.seq_lens[row0 + i] + p.seq_add, p.max_seq));
-    if (seq_len <= 0) {   // only padding rows here: their outputs are defined (zeros), nothing is read
+    // QS: seq_tot tokens are attended to, the last of them (this step's own, at `position`) from registers: the walk covers seq_len = position
+    const int seq_tot = seq_len;
+    const int pos_in = QS ? p.seq_lens[row0] : 0;
+    if constexpr (QS) seq_len = min(max(pos_in, 0), p.max_seq);
+    if (seq_tot <= 0) {   // only padding rows here: their outputs are defined (zeros), nothing is read
         if (part == 0)
             for (int idx = threadIdx.x; idx < nrows * p.G * HD; idx += NTHR) {
                 const int rl = idx / (p.G * HD), rem = idx - rl * (p.G * HD);
@@ -126,7 +164,7 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
             }
         return;
     }
-    if (pstart >= seq_len) return;
+    if (pstart >= seq_tot) return;
     const int pend = min(seq_len, pstart + p.PS);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -142,6 +180,11 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
         const int rl = c * p.R + j / p.G, g = j - (j / p.G) * p.G;
         const bool ok = j < p.R * p.G && rl < nrows;
         const int row = row0 + (ok ? rl : 0);
+        if constexpr (QS) {   // the fragments follow from the slabs (fold_finish below)
+            limit[c] = ok ? seq_len : 0;
+#pragma unroll
+            for (int s = 0; s < NSTEP; ++s) qf[c][s] = (u32x4){0u, 0u, 0u, 0u};
+        } else {
         limit[c] = ok ? min(max(p.seq_lens[row] + p.seq_add, 0), p.max_seq) : 0;
         const f16* qrow = p.q + ((size_t)row * p.nh + kh * p.G + g) * HD;
 #pragma unroll
@@ -150,6 +193,7 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
             u32x4 v = *reinterpret_cast<const u32x4*>(qrow + d);
             if (!ok) v = (u32x4){0u, 0u, 0u, 0u};
             qf[c][s] = v;
+        }
         }
     }
 
@@ -167,7 +211,7 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) qs = act_dot_ones<BF>(v[e], qs);
             }
-            qs = xor32_sum(xor16_sum(qs));
+            qs = at_xor32_sum(at_xor16_sum(qs));
             kq[c] = KVB * qs;
         }
     }
@@ -201,7 +245,7 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
     // n + 2 drained every K/V load of group n + 1 issued just before, so a wave never had a group in flight while it
     // computed (one 16 KB group per ~3.5 us of loaded latency per wave = 4.4 TB/s at b = 64 / ctx 1024).
     struct Wins { int raw[4]; };                       // block ids as loaded (unclamped; clamped where they are used)
-    const int lastw = last & ~7;                       // whole windows are clamped in range (their tokens carry p = 0)
+    const int lastw = (QS ? max(last, 0) : last) & ~7;  // whole windows are clamped in range (their tokens carry p = 0); QS: also with nothing cached
     // window token -> (page index, token inside the page): floor(t / page) as one s_mul_hi with magic = 2^32 / page + 1,
     // exact for t * page < 2^32 (checked on the host)
     auto page_of = [&](int wt) { return (int)__builtin_amdgcn_readfirstlane((int)(((unsigned long long)(unsigned)wt * p.page_magic) >> 32)); };
@@ -317,7 +361,7 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
                     sv[tau * 4 + r] = v;
                     mx = fmaxf(mx, v);
                 }
-            mx = xor32_max(xor16_max(mx));             // the column's 32 tokens sit in the 4 lanes j, j+16, j+32, j+48
+            mx = at_xor32_max(at_xor16_max(mx));             // the column's 32 tokens sit in the 4 lanes j, j+16, j+32, j+48
             // Deferred rescale: the running max is only advanced (and O / l rescaled) when some column's max grew by more than
             // 2^kDefer; until then p = exp2(s - m_run) may exceed 1 by that factor, harmless in fp16 / fp32.  In steady state
             // the per-group multiply of the 32 O accumulators (and their AGPR round trip) disappears.
@@ -375,6 +419,109 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
         }
     };
 
+    // ---- QS: the slab fold.  An item is four NeoX pairs (d .. d + 3, + hd/2) of one head of the block: its G query heads (LDS slots 0 .. G - 1) and,
+    // in the partition that holds `position` (own), the k and v head (slots 16, 17).  A thread owns up to NIT items; their slab, bias and
+    // rotation-row pieces are dense 16-byte loads requested BEFORE the first K/V group (vmcnt returns in order: L2 hits queued behind HBM misses
+    // would wait for them), summed in slab order, rounded as rope_kv.hip rounds, and handed to the four waves through LDS behind ONE barrier.
+    constexpr int IPH = HD / 8, NIT = QS ? (18 * IPH + NTHR - 1) / NTHR : 1;   // items per head; items per thread at G = 16
+    f32x4 fa[NIT][2][4], fc[NIT][2];
+    u32x2 fb[NIT][2];
+    uint16_t* s_new = nullptr;
+    bool own = false, has_new = false;
+    if constexpr (QS) {
+        __shared__ __attribute__((aligned(16))) uint16_t s_new_buf[18 * HD];
+        s_new = s_new_buf;
+        const int pc = min(pos_in, p.max_seq - 1);          // pos_in >= 0 here (seq_tot > 0)
+        own = pstart <= pc && pc < pstart + p.PS;
+        has_new = pos_in < p.max_seq;                       // a position past the attention window is stored (if the table holds it), not attended to
+    }
+    const int pos_lim = QS ? min(p.max_pos, p.max_blocks * p.page) : 1;
+    const int posc = QS ? min(max(pos_in, 0), pos_lim - 1) : 0;   // clamped: the rotation table and the block table stay in range
+    const int nitem = QS ? (p.G + (own ? 2 : 0)) * IPH : 0;
+    auto item_col = [&](int hs) { return (hs < p.G ? kh * p.G + hs : hs == p.G ? p.nh + kh : p.nh + p.nkv + kh) * HD; };
+    auto fold_request = [&]() {
+        const size_t sstride = (size_t)p.B * p.n_pad;
+#pragma unroll
+        for (int k = 0; k < NIT; ++k) {
+            const int it = tid + k * NTHR;
+            const bool on = it < nitem;
+            const int hs = on ? it / IPH : 0, c4 = on ? (it - hs * IPH) * 4 : 0;
+            const int col = item_col(hs) + c4;
+            const float* src = p.slabs + (size_t)row0 * p.n_pad + col;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {               // slabs past the end: re-read the last one, add zero
+                    const int su = min(u, p.nslab - 1);
+                    fa[k][h][u] = on ? *reinterpret_cast<const f32x4*>(src + su * sstride + h * (HD / 2)) : (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+                fb[k][h] = (on && p.bias) ? *reinterpret_cast<const u32x2*>(p.bias + col + h * (HD / 2)) : (u32x2){0u, 0u};
+                // {cos, sin} of the pairs d .. d + 3 (v heads: no rotation)
+                fc[k][h] = (on && hs <= p.G) ? *reinterpret_cast<const f32x4*>(p.cos_sin + ((size_t)posc * (HD / 2) + c4 + 2 * h) * 2)
+                                             : (f32x4){1.f, 0.f, 1.f, 0.f};
+            }
+        }
+    };
+    auto fold_finish = [&]() {
+        const size_t sstride = (size_t)p.B * p.n_pad;
+#pragma unroll
+        for (int k = 0; k < NIT; ++k) {
+            const int it = tid + k * NTHR;
+            const bool on = it < nitem;
+            const int hs = on ? it / IPH : 0, c4 = on ? (it - hs * IPH) * 4 : 0;
+            const int col = item_col(hs) + c4;
+            float x[2][4];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float v = fa[k][h][0][e];
+#pragma unroll
+                    for (int u = 1; u < 4; ++u) v += u < p.nslab ? fa[k][h][u][e] : 0.f;
+                    x[h][e] = v;
+                }
+            for (int su = 4; su < p.nslab; ++su) {          // more than four slabs (shallow-K plans of the row-major launch): the rest, still in index order
+                if (on) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(p.slabs + (size_t)row0 * p.n_pad + col + su * sstride + h * (HD / 2));
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) x[h][e] += v[e];
+                    }
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t bw = fb[k][h][e >> 1];
+                    x[h][e] = act_round<BF>(x[h][e] + ((e & 1) ? act_hi<BF>(bw) : act_lo<BF>(bw)));   // the QKV linear's output is a 16-bit tensor
+                }
+            if (hs <= p.G) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float cs_c = fc[k][e >> 1][(e & 1) * 2], cs_s = fc[k][e >> 1][(e & 1) * 2 + 1];
+                    const float r0 = cs_c * x[0][e] - cs_s * x[1][e];
+                    const float r1 = cs_c * x[1][e] + cs_s * x[0][e];
+                    x[0][e] = r0; x[1][e] = r1;
+                }
+            }
+            u32x2 pk[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) { pk[h][0] = act_pack<BF>(x[h][0], x[h][1]); pk[h][1] = act_pack<BF>(x[h][2], x[h][3]); }
+            if (on) {
+                const int slot = hs < p.G ? hs : 16 + (hs - p.G);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) *reinterpret_cast<u32x2*>(s_new + slot * HD + c4 + h * (HD / 2)) = pk[h];
+            }
+        }
+        __syncthreads();
+        if (j < p.G) {
+#pragma unroll
+            for (int s = 0; s < NSTEP; ++s) qf[0][s] = *reinterpret_cast<const u32x4*>(s_new + j * HD + s * 32 + w * 8);
+        }
+    };
+
     // Two groups in flight per wave (registers ping-pong), block ids looked up one group further ahead:
     // with one long partition per (sequence, kv head) a SIMD holds a single wave, so the wave itself has to
     // keep >= 32 KB of K/V loads outstanding to cover HBM latency.
@@ -398,9 +545,17 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
         Wins w0, w1, w2;
         int tb = pstart + wave * 32;
         if constexpr (NG == 2) {
+            if constexpr (QS) {
+                // the first group is requested by EVERY wave, also one whose share of the partition is empty (clamped windows: valid addresses, never
+                // computed on): behind a guard hipcc's waitcnt pass cannot count these requests and the fold would wait for them (vmcnt(0)) instead
+                // of running while they are in flight
+                fold_request(); __builtin_amdgcn_sched_barrier(0);
+                first_wins(w0); load_group(g0, tb, w0);
+            } else
             if (tb < pend) { first_wins(w0); load_group(g0, tb, w0); }
             AT_STAMP(1);
             if (tb + GS < pend) lookup(tb + GS, w1);
+            if constexpr (QS) { __builtin_amdgcn_sched_barrier(0); fold_finish(); }
             // Steady state without a single condition: both groups of the round and both groups it prefetches lie inside the
             // partition and need no mask.  (Guards around the loads make hipcc's waitcnt pass assume a load may have been
             // issued and never consumed: it then waits for the OTHER group's loads before it reuses a register.)
@@ -489,6 +644,45 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
         }
     }
 
+    if constexpr (QS) {
+        // the new token as a last one-token group of wave 0: K row 0 of the first tile, V slot 0 of window 0, everything else zero and
+        // masked (limit = position + 1 at tb = position leaves exactly that slot visible); the values are the rounded ones the cache got
+        if (has_new && own && wave == 0) {
+            Group gn;
+#pragma unroll
+            for (int s = 0; s < NSTEP; ++s) {
+                gn.kf[0][s] = j == 0 ? *reinterpret_cast<const u32x4*>(s_new + 16 * HD + s * 32 + w * 8) : (u32x4){0u, 0u, 0u, 0u};
+                gn.kf[1][s] = (u32x4){0u, 0u, 0u, 0u};
+            }
+#pragma unroll
+            for (int db = 0; db < NDB; ++db)
+                gn.vf16[db] = (u32x4){w == 0 ? (uint32_t)s_new[17 * HD + db * 16 + j] : 0u, 0u, 0u, 0u};
+            seq_len = pos_in + 1;
+            limit[0] = j < p.G ? pos_in + 1 : 0;
+            compute_group(gn, pos_in, std::true_type{});
+        }
+        // ... and into the cache for later steps: K row-major, V channel-major (native layout), from the LDS copy.  Here, behind the walk, and not in
+        // the prologue: with a global store in front of them the block-table lookups of the walk are no longer provably unclobbered and hipcc turns
+        // them from scalar into vector loads, whose vmcnt waits drain the K/V groups in flight (see lookup above).  Refused and counted as rope_kv.hip does.
+        if (own) {
+            const int new_blk = bt[posc / p.page];
+            const bool store_ok = pos_in == posc && new_blk >= 0 && new_blk < p.num_blocks;
+            const int tok = posc - (posc / p.page) * p.page;
+            if (store_ok) {
+                for (int idx = tid; idx < 2 * (HD / 4); idx += NTHR) {
+                    const bool is_v = idx >= HD / 4;
+                    const int d = (idx - (is_v ? HD / 4 : 0)) * 4;
+                    const u32x2 v = *reinterpret_cast<const u32x2*>(s_new + (is_v ? 17 : 16) * HD + d);
+                    uint16_t* dst = (uint16_t*)const_cast<void*>(p.kv_base) + (((size_t)new_blk * 2 + (is_v ? 1 : 0)) * p.nkv + kh) * head_elems;
+                    if (!is_v) *reinterpret_cast<u32x2*>(dst + (size_t)tok * HD + d) = v;
+                    else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) dst[(size_t)(d + e) * p.page + tok] = (uint16_t)(v[e >> 1] >> ((e & 1) * 16));
+                    }
+                }
+            } else if (kh == 0 && tid == 0 && p.oob_count) atomicAdd(p.oob_count, 1);
+        }
+    }
     AT_STAMP(3);
     // ---- merge the NW waves through LDS, one column tile at a time.  o[c][db][r] is O^T[d = db*16 + w*4 + r][j].
     __shared__ float s_o[NW][16][HD + 4];
@@ -496,13 +690,13 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
 #pragma unroll
     for (int c = 0; c < NT; ++c) {
         float lr = l_run[c];
-        lr = xor32_sum(xor16_sum(lr));
+        lr = at_xor32_sum(at_xor16_sum(lr));
         if (c) __syncthreads();
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
             *reinterpret_cast<f32x4*>(&s_o[wave][j][db * 16 + w * 4]) = o[c][db];
         float l16 = l16_run[c];
-        if (INT8) l16 = xor32_sum(xor16_sum(l16));
+        if (INT8) l16 = at_xor32_sum(at_xor16_sum(l16));
         if (w == 0) { s_m[wave][j] = m_run[c]; s_l[wave][j] = lr; s_b[wave][j] = KVB * l16; }
         __syncthreads();
         AT_STAMP(4);
@@ -644,10 +838,16 @@ extern "C" size_t mi355_paged_attn_workspace_bytes(int32_t B, int32_t nh, int32_
 }
 
 namespace {
+// the QKV projection of the step as split-K slabs (QS instances of the kernel), instead of a q tensor
+struct QkvSlabs {
+    const float* slabs; int nslab, n_pad;
+    const void* bias; const float* cos_sin; int max_pos; int32_t* oob_count;
+};
 int launch_attn(const void* q, const mi355_kv_layer_t* kv, const int32_t* block_table, int32_t max_blocks_per_seq,
                 const int32_t* seq_lens, int32_t seq_lens_minus_one, int32_t B, int32_t q_len, int32_t nh, float scale,
-                int32_t max_seq_len, void* out, void* workspace, size_t workspace_bytes, mi355_stream_t stream, int img_mblk = 0) {
-    MI355_CHECK_ARG(q && kv && kv->kv_base && block_table && seq_lens && out, "paged_attn: null pointer");
+                int32_t max_seq_len, void* out, void* workspace, size_t workspace_bytes, mi355_stream_t stream, int img_mblk = 0,
+                const QkvSlabs* qs = nullptr) {
+    MI355_CHECK_ARG((q || qs) && kv && kv->kv_base && block_table && seq_lens && out, "paged_attn: null pointer");
     MI355_CHECK_KV_LAYOUT(kv, "paged_attn");
     MI355_CHECK_ARG(kv->hd == 64 || kv->hd == 128, "paged_attn: hd=%d (64 or 128)", kv->hd);
     MI355_CHECK_ARG(kv->page >= 16 && kv->page % 8 == 0, "paged_attn: page=%d (>= 16, multiple of 8)", kv->page);
@@ -666,6 +866,11 @@ int launch_attn(const void* q, const mi355_kv_layer_t* kv, const int32_t* block_
     p.page = kv->page; p.max_blocks = max_blocks_per_seq; p.seq_add = seq_lens_minus_one ? 1 : 0;
     p.max_seq = max_seq_len; p.num_blocks = kv->num_blocks;
     p.q_len = q_len; p.R = 16 / p.G; p.img_mblk = img_mblk;
+    p.slabs = nullptr; p.nslab = p.n_pad = 0; p.bias = nullptr; p.cos_sin = nullptr; p.max_pos = 0; p.oob_count = nullptr;
+    if (qs) {
+        p.slabs = qs->slabs; p.nslab = qs->nslab; p.n_pad = qs->n_pad; p.bias = (const f16*)qs->bias; p.cos_sin = qs->cos_sin;
+        p.max_pos = qs->max_pos; p.oob_count = qs->oob_count;
+    }
 #ifdef MI355_TUNING
     p.stamps = g_attn_stamps;
 #endif
@@ -702,11 +907,15 @@ int launch_attn(const void* q, const mi355_kv_layer_t* kv, const int32_t* block_
 #define LR_(LAY_) do { if (bf) { if (kv->hd == 128) LY_(128, true, LAY_); else LY_(64, true, LAY_); } else { if (kv->hd == 128) LY_(128, false, LAY_); else LY_(64, false, LAY_); } } while (0)
 #define LY_(HD_, BF_, LAY_) do { if (NT == 1) hipLaunchKernelGGL((paged_attn_kernel<HD_, false, 1, 4, 2, BF_, LAY_>), grid, dim3(256), 0, st, p); \
                                  else         hipLaunchKernelGGL((paged_attn_kernel<HD_, false, 2, 4, 2, BF_, LAY_>), grid, dim3(256), 0, st, p); } while (0)
-    if (kv->layout == MI355_KV_LAYOUT_REF)           LR_(MI355_KV_LAYOUT_REF);
+    // slab prologue (the caller checked: 16-bit native cache, q_len = 1, hence NT = 1)
+#define LQ_(HD_, BF_) hipLaunchKernelGGL((paged_attn_kernel<HD_, false, 1, 4, 2, BF_, MI355_KV_LAYOUT_NATIVE, true>), grid, dim3(256), 0, st, p)
+    if (qs) { if (bf) { if (kv->hd == 128) LQ_(128, true); else LQ_(64, true); } else { if (kv->hd == 128) LQ_(128, false); else LQ_(64, false); } }
+    else if (kv->layout == MI355_KV_LAYOUT_REF)      LR_(MI355_KV_LAYOUT_REF);
     else if (kv->layout == MI355_KV_LAYOUT_REF_VVEC) LR_(MI355_KV_LAYOUT_REF_VVEC);
     else if (bf)       { if (kv->hd == 128) { if (int8) LB_(128, true); else LB_(128, false); } else { if (int8) LB_(64, true); else LB_(64, false); } }
     else if (kv->hd == 128) { if (int8) L2_(128, true); else L2_(128, false); }
     else               { if (int8) L2_(64, true);  else L2_(64, false); }
+#undef LQ_
 #undef LY_
 #undef LR_
 #undef LB_
@@ -759,4 +968,26 @@ extern "C" int mi355_paged_attn_rows_img(const void* q, const mi355_kv_layer_t* 
     MI355_CHECK_ARG(B > 0 && q_len > 0 && B * q_len <= 64 && kv && (nh * kv->hd) % 32 == 0, "paged_attn_rows_img: %d x %d rows (<= 64)", B, q_len);
     return launch_attn(q, kv, block_table, max_blocks_per_seq, positions, 1, B, q_len, nh, scale, max_seq_len, out_img, workspace,
                        workspace_bytes, stream, cdiv(B * q_len, 16));
+}
+
+// Decode attention that takes the step's QKV projection as fp32 split-K slabs [nslab][B][n_pad] (mi355_linear_partial_img / mi355_linear_partial)
+// instead of a q tensor: bias + RoPE + KV write happen in the attention launch's prologue (paged_attn_kernel, QS).  out_img as
+// mi355_paged_attn_rows_img.  16-bit caches in the native block layout, q_len = 1; anything else: MI355_ERR_UNSUPPORTED, nothing launched.
+extern "C" int mi355_paged_attn_qkv_slabs_img(const float* slabs, int32_t nslab, int32_t n_pad, const void* qkv_bias, const float* cos_sin,
+                                              int32_t rope_dim, int32_t max_pos, const mi355_kv_layer_t* kv, const int32_t* block_table,
+                                              int32_t max_blocks_per_seq, const int32_t* positions, int32_t B, int32_t q_len, int32_t nh,
+                                              float scale, int32_t max_seq_len, void* out_img, void* workspace, size_t workspace_bytes,
+                                              int32_t* oob_count, mi355_stream_t stream) {
+    MI355_CHECK_ARG(slabs && cos_sin && kv && kv->kv_base && block_table && positions && out_img, "paged_attn_qkv_slabs_img: null pointer");
+    MI355_CHECK_KV_LAYOUT(kv, "paged_attn_qkv_slabs_img");
+    MI355_CHECK_ARG(B > 0 && q_len > 0 && nh > 0 && kv->nkv > 0 && nh % kv->nkv == 0 && max_pos > 0 && max_blocks_per_seq > 0,
+                    "paged_attn_qkv_slabs_img: B=%d q_len=%d nh=%d nkv=%d max_pos=%d", B, q_len, nh, kv->nkv, max_pos);
+    if (kv->kv_dtype == MI355_KV_INT8 || kv->layout != MI355_KV_LAYOUT_NATIVE || q_len != 1 || rope_dim != kv->hd || B > 64) return MI355_ERR_UNSUPPORTED;
+    MI355_CHECK_ARG(nslab >= 1 && nslab <= 16 && n_pad % 4 == 0 && (long)n_pad >= (long)(nh + 2 * kv->nkv) * kv->hd && ((uintptr_t)slabs & 15) == 0,
+                    "paged_attn_qkv_slabs_img: nslab=%d (1..16), n_pad=%d (multiple of 4, >= (nh + 2 nkv) hd), slabs 16-byte aligned", nslab, n_pad);
+    MI355_CHECK_ARG((nh * kv->hd) % 32 == 0 && (!qkv_bias || ((uintptr_t)qkv_bias & 7) == 0) && ((uintptr_t)cos_sin & 15) == 0,
+                    "paged_attn_qkv_slabs_img: nh * hd %% 32, bias 8-byte and rotation table 16-byte aligned");
+    const QkvSlabs qs = {slabs, nslab, n_pad, qkv_bias, cos_sin, max_pos, oob_count};
+    return launch_attn(nullptr, kv, block_table, max_blocks_per_seq, positions, 1, B, 1, nh, scale, max_seq_len, out_img, workspace,
+                       workspace_bytes, stream, cdiv(B, 16), &qs);
 }

@@ -14,6 +14,7 @@
 //   class                                                 | QKV                                           | O                                   | gate_up                  | down                                | partial sums + residual + next norm
 //   tp 1, <= fuse_rows (W4, fp16 step: gemm_fullk.hip)    | qkv_rope_kv_write [norm on load from layer 1] | linear_residual [+ sums of squares] | norm_linear              | linear_residual [+ sums of squares] | in the epilogues (rmsnorm launch: no fused norm; the final norm)
 //   tp 1, > fuse_rows: images (fullk64 / wide / splitk64) | qkv_rope_kv_write_img                         | linear_residual_prenorm_img         | linear_deferred_norm_img | linear_partial_img (4 K quarters)   | add_rmsnorm_img_touch (final norm: add_rmsnorm)
+//     ... opt-in (set_qkv_slab_rows): q_len 1, native cache| linear_partial_img (slabs -> attention)       | "                                   | "                        | "                                   | "
 //     ... gate_up / down without their image launch       | "                                             | linear_residual_img + rmsnorm       | linear_direct            | linear_partial                      | "
 //     ... INT8 cache, Qwen3 QK norm                       | linear_partial + rope_kv_write_rows[_qk_norm] | "                                   | "                        | "                                   | add_rmsnorm
 //   other formats: staged split-K                         | linear_partial + rope_kv_write_rows           | linear_partial                      | linear_direct            | linear_partial                      | add_rmsnorm
@@ -21,7 +22,8 @@
 //   TP attached, > tp_fuse_rows, slabs                    | qkv_rope_kv_write_img                         | linear_partial                      | linear_direct[_img]      | linear_partial_img                  | allreduce_fused_img
 //   TP attached, <= tp_fuse_rows                          | qkv_rope_kv_write, or as staged               | linear_partial                      | linear_direct            | linear_partial                      | allreduce_fused
 //   TP, external transport / segment caller               | "                                             | linear_partial                      | linear_direct            | linear_partial                      | add_rmsnorm (fold -> ar_buf) + all-reduce; add_rmsnorm opens the next segment
-// Between QKV and O: paged_attn_rows (+ partition reduce), as paged_attn_rows_img where the O launch reads an image.  Activations are handed over row-major
+// Between QKV and O: paged_attn_rows (+ partition reduce), as paged_attn_rows_img where the O launch reads an image; behind the slab row of QKV
+// paged_attn_qkv_slabs_img, whose prologue folds the slabs, adds the bias, rotates and writes the new token's k / v (no q tensor, no writer launch).  Activations are handed over row-major
 // or as fragment-ordered images (common.h act_img_index); no standalone reduce / add / activation kernels.  The KV block layout (mi355_decoder_set_kv_layout)
 // is not a column: every cell that touches a cache takes it through kv_of, which carries the layout -- the same launches, other addresses.
 #include <hip/hip_runtime.h>
@@ -53,13 +55,15 @@ inline size_t weight_bytes(const mi355_weight_t* w) { return (size_t)w->K_pad * 
 struct LaunchCaps {
     bool fuse_qkv, fuse_o, fuse_down, fuse_norm;   // few-row full-K launches with their consumer fused (gemm_fullk.hip)
     bool img_qkv, img_o, img_gate_up, img_down;    // tp = 1: launches on activation images (gemm_fullk64 / gemm_wide / gemm_splitk64.hip)
+    bool slab_qkv, slab_qkv_img;                   // tp = 1: QKV as split-K slabs folded in the attention launch's prologue; ... produced from the image (else from row-major xn)
+    int  slab_rows;                                // ... from this many rows of a q_len = 1 step
     bool tp_img_qkv, tp_img_down, tp_img_gate;     // the same launches for the shards of a TP step with the all-reduce context attached
     bool tp_pub_o, tp_pub_down;                    // row-parallel shards published straight into the registered all-reduce buffer
     int  fuse_rows, tp_fuse_rows;                  // up to this many rows the (TP) step keeps the few-row launches
 };
 // The launch chain of ONE step: one selector per stage, resolved in mi355_decoder_begin_rows (resolve_step) and read by every launch
 // site.  Each activation hand-over has one layout flag, derived from its CONSUMER's selector; producer and consumer both read it.
-enum class QkvSel  { IMG, FULLK, SPLITK };
+enum class QkvSel  { IMG, FULLK, SPLITK, ATTN_SLABS };
 enum class OSel    { PUBLISH, IMG_PRENORM, IMG, FULLK, SPLITK };
 enum class GateSel { DEFERRED_NORM_IMG, NORM_ON_LOAD, DIRECT_IMG, DIRECT };
 enum class DownSel { FULLK, PUBLISH, QUARTERS, SPLITK };
@@ -264,6 +268,14 @@ int plan_launches(mi355_decoder* d) {
     for (const auto& L : d->layers) {   // the launchers' own predicate (gemm.hip)
         k.img_qkv = k.img_qkv && mi355_fullk64_weight_ok(&L.qkv) != 0; k.img_o = k.img_o && mi355_fullk64_weight_ok(&L.o) != 0;
     }
+    // QKV as a plain split-K launch whose slabs the attention launch folds itself (bias, RoPE, KV write in its prologue: attention.hip, QS): what
+    // the fused launch is fusable for, with the attention output as an image.  The slabs come from the image (gemm_splitk64.hip) where that launch has a
+    // plan for the shape, else from the staged kernel on row-major rows (narrow models: K too short for eight K slices per block)
+    k.slab_qkv = k.img_qkv && k.img_o;
+    k.slab_qkv_img = k.slab_qkv;
+    for (const auto& L : d->layers)
+        k.slab_qkv_img = k.slab_qkv_img && L.qkv.K % 128 == 0 && L.qkv.K_pad == L.qkv.K &&
+                         mi355_gemm_splitk64_plan(64, L.qkv.N_pad / 16, L.qkv.K_pad / 128, L.qkv.wbits, L.qkv.group_size, kMaxSplits, nullptr) > 0;
     // ... the post-attention RMSNorm deferred into gate_up's accumulators (mi355_deferred_norm_t): the O launch leaves gamma 2^-e h' as an image + the
     // per-tile sums of h'^2, the wide GEMM applies rsqrt(mean h'^2 + eps) 2^e: 6 launches per layer
     k.img_gate_up = k.img_o && c.hidden % 64 == 0 && TUNE(5) != 3;
@@ -306,6 +318,10 @@ int plan_launches(mi355_decoder* d) {
     // rows.  Without the image path (other weight formats, TP) the earlier crossover to the staged kernels stays: 12
     k.fuse_rows = !(k.img_qkv && k.img_o) ? 12 : (bf_act || !(k.fuse_qkv && k.fuse_o && k.fuse_down)) ? 0 : 4;
     if (TUNE(6) > 0) k.fuse_rows = TUNE(6) == 99 ? 0 : TUNE(6);   // tuning build: crossover experiments (tools/batch_sweep.py --tune 6=N)
+    // slab_rows: from how many rows the decode step takes the slab row of the table; 0 = never, the default.  The path sums K in another order (3 slabs of
+    // 8 wave slices instead of 14 slices) and adds the new token to the softmax last, so its logits differ from the fused launch's in the last bits -- and a
+    // greedy decode of many steps amplifies a last bit into other tokens.  A caller opts in with mi355_decoder_set_qkv_slab_rows; DESIGN 9 D has what it measured.
+    k.slab_rows = 0;
     // tp_fuse_rows: from how many rows the TP step takes the image launches.  With the down shard as K quarters they win from ONE row (one rank of tp 2,
     // b = 1 / 2 / 4: 1.67 / 1.68 / 1.72 ms against 1.75 / 1.77 / 1.82 with the few-row QKV launch + 15 staged slabs;
     // profiles/r05_tp_small_batch_crossover.txt); without that plan the few-row QKV launch (row-major input) keeps its rows (the tp = 1 crossover)
@@ -486,7 +502,7 @@ bool pub_ready(const mi355_decoder* d, int B) {
 
 // The launch chain of a B-row step: the row of the table at the top of this file.  Consumers first; every layout flag follows from
 // its consumer's selector and from nothing else.
-int resolve_step(mi355_decoder* d, int B) {
+int resolve_step(mi355_decoder* d, int B, int q_len) {
     const LaunchCaps& k = d->caps;
     StepPlan p;
     p.meet = d->cfg.tp_size == 1 ? MeetSel::LOCAL : d->ar ? MeetSel::FUSED_AR : MeetSel::EXT;
@@ -494,7 +510,8 @@ int resolve_step(mi355_decoder* d, int B) {
     const bool mid = B > k.fuse_rows;                                        // tp = 1 step on the image launches (img_* are tp = 1 only)
     const bool few = !(k.tp_img_qkv && tp_mid) && !mid;                      // the few-row full-K launches keep their rows
     const bool pub = tp_mid && (k.tp_pub_o || k.tp_pub_down) && pub_ready(d, B);
-    p.qkv = ((k.img_qkv && mid) || (k.tp_img_qkv && tp_mid)) ? QkvSel::IMG : (k.fuse_qkv && few) ? QkvSel::FULLK : QkvSel::SPLITK;
+    const bool slabs = k.slab_qkv && k.slab_rows > 0 && mid && q_len == 1 && B >= k.slab_rows && d->kv_layout == MI355_KV_LAYOUT_NATIVE;
+    p.qkv = slabs ? QkvSel::ATTN_SLABS : ((k.img_qkv && mid) || (k.tp_img_qkv && tp_mid)) ? QkvSel::IMG : (k.fuse_qkv && few) ? QkvSel::FULLK : QkvSel::SPLITK;
     p.resid_ssq = k.fuse_norm && few;
     p.gate_up = (k.img_o && k.img_gate_up && mid) ? GateSel::DEFERRED_NORM_IMG : p.resid_ssq ? GateSel::NORM_ON_LOAD
               : (k.tp_img_gate && tp_mid) ? GateSel::DIRECT_IMG : GateSel::DIRECT;
@@ -503,7 +520,7 @@ int resolve_step(mi355_decoder* d, int B) {
         : (k.fuse_o && few) ? OSel::FULLK : OSel::SPLITK;
     p.down = (k.fuse_down && few) ? DownSel::FULLK : (k.tp_pub_down && pub) ? DownSel::PUBLISH
            : ((p.gate_up == GateSel::DEFERRED_NORM_IMG && k.img_down) || (k.tp_img_down && tp_mid)) ? DownSel::QUARTERS : DownSel::SPLITK;
-    p.xn_is_image = p.qkv == QkvSel::IMG;
+    p.xn_is_image = p.qkv == QkvSel::IMG || (p.qkv == QkvSel::ATTN_SLABS && k.slab_qkv_img);
     p.attn_is_image = p.o == OSel::PUBLISH || p.o == OSel::IMG_PRENORM || p.o == OSel::IMG;
     p.gate_in_is_image = p.gate_up == GateSel::DEFERRED_NORM_IMG || p.gate_up == GateSel::DIRECT_IMG;
     p.act_is_image = p.down == DownSel::PUBLISH || p.down == DownSel::QUARTERS;
@@ -511,6 +528,7 @@ int resolve_step(mi355_decoder* d, int B) {
     const bool ar_tail = p.meet == MeetSel::FUSED_AR && (p.o == OSel::PUBLISH || p.o == OSel::SPLITK);   // the all-reduce launch writes either layout
     const char* bad =
         p.xn_is_image && p.meet == MeetSel::EXT ? "QKV on an image behind the external transport's row-major norm" :
+        p.qkv == QkvSel::ATTN_SLABS && !(p.attn_is_image && p.meet == MeetSel::LOCAL && q_len == 1) ? "QKV slabs for the attention prologue without its image output, under TP or with q_len > 1" :
         p.resid_ssq && !(p.qkv == QkvSel::FULLK && p.o == OSel::FULLK && p.down == DownSel::FULLK) ? "norm on load without the full-K launches that leave the sums of squares" :
         (p.gate_up == GateSel::DEFERRED_NORM_IMG) != (p.o == OSel::IMG_PRENORM) ? "deferred norm in gate_up without the O launch that prepares it" :
         p.gate_up == GateSel::DIRECT_IMG && !ar_tail ? "gate_up on an image no launch writes" :
@@ -568,6 +586,22 @@ extern "C" void mi355_decoder_destroy(mi355_decoder_t* d) {
     delete d;
 }
 
+// Which QKV cell of the launch table the step in flight (or last begun) took: 0 image launch, 1 few-row full-K launch, 2 split-K + writer launch,
+// 3 split-K slabs folded in the attention prologue; MI355_ERR_ARG before the first step.  Read-only: tests assert the plan they mean to exercise.
+extern "C" int mi355_decoder_qkv_launch(const mi355_decoder_t* d) {
+    if (!d || d->B <= 0) { mi355_set_error("decoder_qkv_launch: no step begun"); return MI355_ERR_ARG; }
+    return (int)d->plan.qkv;
+}
+
+// From how many rows a decode step (q_len = 1) takes its QKV projection as split-K slabs folded in the attention prologue, where the configuration allows
+// that path at all (plan_launches: slab_qkv); below, the fused QKV launch stays.  rows <= 0: never (the default).  Captured steps bake the chain in: dropped.
+extern "C" int mi355_decoder_set_qkv_slab_rows(mi355_decoder_t* d, int32_t rows) {
+    if (!d) { mi355_set_error("decoder_set_qkv_slab_rows: null decoder"); return MI355_ERR_ARG; }
+    drop_graphs(d);
+    d->caps.slab_rows = rows > 0 ? rows : 0;
+    return MI355_OK;
+}
+
 extern "C" int mi355_decoder_begin(mi355_decoder_t* d, int32_t B, mi355_stream_t stream) {
     return mi355_decoder_begin_rows(d, B, 1, stream);
 }
@@ -579,7 +613,7 @@ extern "C" int mi355_decoder_begin_rows(mi355_decoder_t* d, int32_t nseq, int32_
                         "(larger batches: mi355_decoder_step)", nseq, q_len);
         return MI355_ERR_ARG;
     }
-    if (int e = resolve_step(d, B)) return e;
+    if (int e = resolve_step(d, B, q_len)) return e;
     hipStream_t st = (hipStream_t)stream;
     d->B = B; d->q_len = q_len; d->started = true;
     const auto& c = d->cfg; const StepPlan& p = d->plan;
@@ -676,6 +710,11 @@ extern "C" int mi355_decoder_layer_attn(mi355_decoder_t* d, int32_t l, mi355_str
         PF_ISSUE(MI355_PF_O | MI355_PF_O_LATE, &L.o);
         break;
     }
+    case QkvSel::ATTN_SLABS:   // a plain split-K launch: bias, RoPE and the KV write wait in the attention launch, where a block owns whole heads
+        if (p.xn_is_image) RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial_img(d->xn_img, B, &L.qkv, d->partials, kMaxSplits, st));
+        else               RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial(d->xn, B, &L.qkv, d->partials, kMaxSplits, st));
+        PF_ISSUE(MI355_PF_O | MI355_PF_O_LATE, &L.o);
+        break;
     case QkvSel::SPLITK:
         RUN(MI355_KC_GEMM_QUANT, ns = mi355_linear_partial(d->xn, B, &L.qkv, d->partials, kMaxSplits, st));
         PF_ISSUE(MI355_PF_O, &L.o);          // under RoPE + attention
@@ -692,6 +731,12 @@ extern "C" int mi355_decoder_layer_attn(mi355_decoder_t* d, int32_t l, mi355_str
         break;
     }
     // q_len > 1: rows of one sequence share a pass over its KV, causal mask inside the page walk (is_target_verify)
+    if (p.qkv == QkvSel::ATTN_SLABS)   // q_buf is not written on this path: the launch takes q from the slabs (and nothing else reads q_buf)
+        RUN(MI355_KC_ATTN, mi355_paged_attn_qkv_slabs_img(d->partials, ns, L.qkv.N_pad, L.qkv_bias, d->model.cos_sin, c.rope_dim, c.max_pos, &kv,
+                                                          d->bufs.block_table, c.max_blocks_per_seq, d->bufs.positions, B, d->q_len, c.nh,
+                                                          1.0f / sqrtf((float)c.hd), c.max_seq_len, d->attn_img, d->attn_ws, d->attn_ws_bytes,
+                                                          d->oob_count, st));
+    else
     RUN(MI355_KC_ATTN, (p.attn_is_image ? mi355_paged_attn_rows_img : mi355_paged_attn_rows)(
                            d->q_buf, &kv, d->bufs.block_table, c.max_blocks_per_seq, d->bufs.positions, B / d->q_len, d->q_len, c.nh,
                            1.0f / sqrtf((float)c.hd), c.max_seq_len, p.attn_is_image ? d->attn_img : d->attn_out, d->attn_ws, d->attn_ws_bytes, st));

@@ -563,6 +563,15 @@ class DecoderEngine:
             _C.check(int(n), "decoder_oob_count")
         return int(n)
 
+    def qkv_launch(self) -> int:
+        """Which QKV launch the step begun last took (mi355_decoder_qkv_launch): 0 image launch, 1 few-row full-K launch, 2 split-K +
+        writer launch, 3 split-K slabs folded in the attention prologue."""
+        return _C.check(self.lib.mi355_decoder_qkv_launch(self.handle), "decoder_qkv_launch")
+
+    def set_qkv_slab_rows(self, rows: int):
+        """Opt in: from `rows` rows a decode step folds the QKV slabs in the attention prologue (mi355_decoder_set_qkv_slab_rows; <= 0: off, the default)."""
+        _C.check(self.lib.mi355_decoder_set_qkv_slab_rows(self.handle, int(rows)), "decoder_set_qkv_slab_rows")
+
     # ---- tp = 1
     def step(self, B: int):
         _C.check(self.lib.mi355_decoder_step(self.handle, B, self._st()), "decoder_step")

@@ -241,6 +241,29 @@ def paged_attention_rows_img(q: torch.Tensor, kv_base, scale_base, block_table: 
     return img
 
 
+def paged_attention_qkv_slabs_img(slabs: torch.Tensor, qkv_bias, cos_sin, positions: torch.Tensor, block_table: torch.Tensor, kv_base,
+                                  scale_base, nh: int, nkv: int, hd: int, page: int, max_seq_len: int, q_len: int = 1,
+                                  oob_count: Optional[torch.Tensor] = None, scale: Optional[float] = None, *,
+                                  layout: int = _C.KV_LAYOUT_NATIVE) -> Optional[ActImage]:
+    """Decode attention on the QKV projection's fp32 split-K slabs [n, T, N_pad] (linear_partial_img): bias + RoPE + KV write in the
+    launch's prologue, the output as an activation image; None when the configuration is not taken (INT8 cache, reference layout,
+    q_len > 1)."""
+    _chk(slabs, torch.float32, "paged_attention_qkv_slabs_img.slabs"); _chk(block_table, torch.int32, "block_table"); _chk(positions, torch.int32, "positions")
+    n, T, n_pad = slabs.shape
+    act = _act_of_cache(kv_base) if kv_base.dtype != torch.int8 else torch.float16
+    kv = kv_struct(kv_base, scale_base, page, nkv, hd, act, layout=layout)
+    img = _new_image(T, nh * hd, torch.float16, slabs.device, act)
+    ws = _workspace(_C.lib().mi355_paged_attn_workspace_bytes(T, nh, hd, max_seq_len), slabs.device)
+    rc = _C.lib().mi355_paged_attn_qkv_slabs_img(slabs.data_ptr(), n, n_pad, _p(qkv_bias), cos_sin.data_ptr(), hd, cos_sin.shape[0], C.byref(kv),
+                                                 block_table.data_ptr(), block_table.shape[1], positions.data_ptr(), T // q_len, q_len, nh,
+                                                 scale if scale is not None else 1.0 / math.sqrt(hd), max_seq_len, img.data.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _p(oob_count), _stream())
+    if rc == ERR_UNSUPPORTED:
+        return None
+    _C.check(rc, "paged_attn_qkv_slabs_img")
+    return img
+
+
 def linear_residual_img(x: ActImage, w: PackedWeight, residual: torch.Tensor, bias: Optional[torch.Tensor] = None,
                         out: Optional[torch.Tensor] = None, tile_sumsq: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """linear_residual for 1-64 rows (the step driver: from 5) with the activations as an image (gemm_fullk64.hip); None when the shape is not taken."""
