@@ -25,6 +25,12 @@ HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-fno-slp-vectorize", "-Wno-unused-result", "-x", "hip"]
+# Kernarg preload: the leading scalar kernel parameters arrive in user SGPRs at wave start, so a kernel's first
+# address arithmetic needs no s_load of the argument segment.  Reaches only parameters passed individually, never a by-value struct.
+# MI355_KERNARG_PRELOAD=0 omits the flag (A/B builds from one tree; changing it needs --force, objects do not record it).
+KERNARG_PRELOAD = os.environ.get("MI355_KERNARG_PRELOAD", "1") != "0"
+if KERNARG_PRELOAD:
+    CFLAGS += ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
 def _stale(src, obj):

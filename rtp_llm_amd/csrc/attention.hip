@@ -63,6 +63,27 @@ struct AttnParams {
 #else
 #define AT_STAMP(i) do { } while (0)
 #endif
+// Launch heads (kernarg preload): the fields a wave consumes before its first scalar request -- the block-id and context-length lookups of
+// paged_attn_kernel, the length / (max, sum) / partial-row requests of attn_reduce_kernel -- travel as the kernels' LEADING SCALAR parameters, which arrive
+// in SGPRs at wave start (13 and 10 dwords of the 14 next to the kernarg segment pointer); a by-value struct is never preloaded, so the whole AttnParams
+// follows them and the kernels' first lines put the head back.  kv_base is not in the head: the first K/V request waits for the block ids anyway.
+#define ATTN_HEAD_PARAMS const int32_t* h_block_table, const int32_t* h_seq_lens, int h_ntile, int h_max_blocks, int h_PS, int h_page, uint32_t h_page_magic, \
+                         int h_q_len, int h_R, int h_seq_add, int h_max_seq
+#define ATTN_HEAD_BIND(p)                                                                                                                       \
+    do { (p).block_table = h_block_table; (p).seq_lens = h_seq_lens; (p).ntile = h_ntile; (p).max_blocks = h_max_blocks; (p).PS = h_PS; (p).page = h_page; \
+         (p).page_magic = h_page_magic; (p).q_len = h_q_len; (p).R = h_R; (p).seq_add = h_seq_add; (p).max_seq = h_max_seq; } while (0)
+#define ATTN_REDUCE_HEAD_PARAMS const int32_t* h_seq_lens, const float* h_tmp_ml, const float* h_tmp_out, int h_B, int h_q_len, int h_nh, int h_P
+#define ATTN_REDUCE_HEAD_BIND(p) \
+    do { (p).seq_lens = h_seq_lens; (p).tmp_ml = const_cast<float*>(h_tmp_ml); (p).tmp_out = const_cast<float*>(h_tmp_out); (p).B = h_B; (p).q_len = h_q_len; (p).nh = h_nh; (p).P = h_P; } while (0)
+// the one place per kernel that splits a filled AttnParams into head + rest
+template <class Kernel>
+inline void launch_attn_head(Kernel k, dim3 grid, dim3 block, hipStream_t st, const AttnParams& p) {
+    hipLaunchKernelGGL(k, grid, block, 0, st, p.block_table, p.seq_lens, p.ntile, p.max_blocks, p.PS, p.page, p.page_magic, p.q_len, p.R, p.seq_add, p.max_seq, p);
+}
+template <class Kernel>
+inline void launch_attn_reduce_head(Kernel k, dim3 grid, dim3 block, hipStream_t st, const AttnParams& p) {
+    hipLaunchKernelGGL(k, grid, block, 0, st, p.seq_lens, (const float*)p.tmp_ml, (const float*)p.tmp_out, p.B, p.q_len, p.nh, p.P, p);
+}
 // element index of out[row][col], col = h * HD + d
 __device__ __forceinline__ size_t out_index(const AttnParams& p, int row, int col, int HD) {
     return p.img_mblk > 0 ? act_img_index(row, col, p.img_mblk) : (size_t)row * p.nh * HD + col;
@@ -118,7 +139,9 @@ __device__ __forceinline__ f16x8 widen_kv8(uint32_t lo, uint32_t hi) {
 // [0, position); the new token's k / v are stored for later steps and enter THIS step as a last one-token group built from the same
 // rounded 16-bit values in registers: nothing this launch stores is read back by it.  false compiles to the kernel without it.
 template <int HD, bool INT8, int NT, int NW, int NG, bool BF = false, int LAY = MI355_KV_LAYOUT_NATIVE, bool QS = false>
-__global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p) {
+__global__ __launch_bounds__(64 * NW) void paged_attn_kernel(ATTN_HEAD_PARAMS, const AttnParams rest) {
+    AttnParams p = rest;                           // the launch head arrives in SGPRs; everything below reads the struct as before
+    ATTN_HEAD_BIND(p);
     static_assert(LAY == MI355_KV_LAYOUT_NATIVE || !INT8, "the reference layouts are 16-bit caches");
     static_assert(!QS || (!INT8 && NT == 1 && NW == 4 && NG == 2 && LAY == MI355_KV_LAYOUT_NATIVE), "slab prologue: 16-bit native cache, one row per sequence");
     constexpr bool KREF = LAY != MI355_KV_LAYOUT_NATIVE;       // K as [hd/8][page][8]: a lane's piece is one 8-channel chunk of one token
@@ -742,7 +765,9 @@ __global__ __launch_bounds__(64 * NW) void paged_attn_kernel(const AttnParams p)
 
 // Merge partitions: one wave per (sequence, head); lane owns HD/64 channels.
 template <int HD, bool BF = false>
-__global__ __launch_bounds__(256) void attn_reduce_kernel(const AttnParams p) {
+__global__ __launch_bounds__(256) void attn_reduce_kernel(ATTN_REDUCE_HEAD_PARAMS, const AttnParams rest) {
+    AttnParams p = rest;
+    ATTN_REDUCE_HEAD_BIND(p);
     const int lane = threadIdx.x & 63;
     const int gid = blockIdx.x * 4 + (threadIdx.x >> 6); // (row, h)
     if (gid >= p.B * p.q_len * p.nh) return;
@@ -889,7 +914,7 @@ int launch_attn(const void* q, const mi355_kv_layer_t* kv, const int32_t* block_
     p.tmp_ml  = p.tmp_out + rows * nh * p.P * kv->hd;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(p.P, kv->nkv, B * p.ntile);
-#define L_(HD_, I8_, NT_, NW_, NG_) hipLaunchKernelGGL((paged_attn_kernel<HD_, I8_, NT_, NW_, NG_>), grid, dim3(64 * NW_), 0, st, p)
+#define L_(HD_, I8_, NT_, NW_, NG_) launch_attn_head((paged_attn_kernel<HD_, I8_, NT_, NW_, NG_>), grid, dim3(64 * NW_), st, p)
 #ifdef MI355_TUNING
 #define L2_(HD_, I8_) do { if (NT == 1) { if (TUNE(6) == 3) L_(HD_, I8_, 1, 4, 3); else if (TUNE(6) == 4) L_(HD_, I8_, 1, 4, 4); else if (TUNE(6) == 2) L_(HD_, I8_, 1, 4, 2); \
                                             else if (TUNE(6) == 8) L_(HD_, I8_, 1, 8, 2); else if (TUNE(6) == 9) L_(HD_, I8_, 1, 8, 3); else L_(HD_, I8_, 1, 4, (I8_ ? 4 : 2)); } else L_(HD_, I8_, 2, 4, 2); } while (0)
@@ -901,14 +926,14 @@ int launch_attn(const void* q, const mi355_kv_layer_t* kv, const int32_t* block_
     const bool bf = kv->act_dtype == MI355_ACT_BF16;
     MI355_CHECK_ARG(kv->act_dtype == MI355_ACT_F16 || bf, "paged_attn: act_dtype=%d", kv->act_dtype);
     MI355_CHECK_ARG(int8 || (bf == (kv->kv_dtype == MI355_KV_BF16)), "paged_attn: a 16-bit cache has the dtype of the activations");
-#define LB_(HD_, I8_) do { if (NT == 1) hipLaunchKernelGGL((paged_attn_kernel<HD_, I8_, 1, 4, (I8_ ? 4 : 2), true>), grid, dim3(256), 0, st, p); \
-                           else         hipLaunchKernelGGL((paged_attn_kernel<HD_, I8_, 2, 4, 2, true>), grid, dim3(256), 0, st, p); } while (0)
+#define LB_(HD_, I8_) do { if (NT == 1) launch_attn_head((paged_attn_kernel<HD_, I8_, 1, 4, (I8_ ? 4 : 2), true>), grid, dim3(256), st, p); \
+                           else         launch_attn_head((paged_attn_kernel<HD_, I8_, 2, 4, 2, true>), grid, dim3(256), st, p); } while (0)
     // a reference layout (16-bit caches only, checked above): the instantiation the native cache of the same shape takes, with the layout's addressing
 #define LR_(LAY_) do { if (bf) { if (kv->hd == 128) LY_(128, true, LAY_); else LY_(64, true, LAY_); } else { if (kv->hd == 128) LY_(128, false, LAY_); else LY_(64, false, LAY_); } } while (0)
-#define LY_(HD_, BF_, LAY_) do { if (NT == 1) hipLaunchKernelGGL((paged_attn_kernel<HD_, false, 1, 4, 2, BF_, LAY_>), grid, dim3(256), 0, st, p); \
-                                 else         hipLaunchKernelGGL((paged_attn_kernel<HD_, false, 2, 4, 2, BF_, LAY_>), grid, dim3(256), 0, st, p); } while (0)
+#define LY_(HD_, BF_, LAY_) do { if (NT == 1) launch_attn_head((paged_attn_kernel<HD_, false, 1, 4, 2, BF_, LAY_>), grid, dim3(256), st, p); \
+                                 else         launch_attn_head((paged_attn_kernel<HD_, false, 2, 4, 2, BF_, LAY_>), grid, dim3(256), st, p); } while (0)
     // slab prologue (the caller checked: 16-bit native cache, q_len = 1, hence NT = 1)
-#define LQ_(HD_, BF_) hipLaunchKernelGGL((paged_attn_kernel<HD_, false, 1, 4, 2, BF_, MI355_KV_LAYOUT_NATIVE, true>), grid, dim3(256), 0, st, p)
+#define LQ_(HD_, BF_) launch_attn_head((paged_attn_kernel<HD_, false, 1, 4, 2, BF_, MI355_KV_LAYOUT_NATIVE, true>), grid, dim3(256), st, p)
     if (qs) { if (bf) { if (kv->hd == 128) LQ_(128, true); else LQ_(64, true); } else { if (kv->hd == 128) LQ_(128, false); else LQ_(64, false); } }
     else if (kv->layout == MI355_KV_LAYOUT_REF)      LR_(MI355_KV_LAYOUT_REF);
     else if (kv->layout == MI355_KV_LAYOUT_REF_VVEC) LR_(MI355_KV_LAYOUT_REF_VVEC);
@@ -925,10 +950,10 @@ int launch_attn(const void* q, const mi355_kv_layer_t* kv, const int32_t* block_
     if (p.P > 1) {
         const int nblk = cdiv((int)rows * nh, 4);
         if (bf) {
-            if (kv->hd == 128) hipLaunchKernelGGL((attn_reduce_kernel<128, true>), dim3(nblk), dim3(256), 0, st, p);
-            else               hipLaunchKernelGGL((attn_reduce_kernel<64, true>), dim3(nblk), dim3(256), 0, st, p);
-        } else if (kv->hd == 128) hipLaunchKernelGGL(attn_reduce_kernel<128>, dim3(nblk), dim3(256), 0, st, p);
-        else               hipLaunchKernelGGL(attn_reduce_kernel<64>, dim3(nblk), dim3(256), 0, st, p);
+            if (kv->hd == 128) launch_attn_reduce_head((attn_reduce_kernel<128, true>), dim3(nblk), dim3(256), st, p);
+            else               launch_attn_reduce_head((attn_reduce_kernel<64, true>), dim3(nblk), dim3(256), st, p);
+        } else if (kv->hd == 128) launch_attn_reduce_head((attn_reduce_kernel<128>), dim3(nblk), dim3(256), st, p);
+        else               launch_attn_reduce_head((attn_reduce_kernel<64>), dim3(nblk), dim3(256), st, p);
         MI355_CHECK_LAUNCH("attn_reduce_kernel");
     }
     return MI355_OK;

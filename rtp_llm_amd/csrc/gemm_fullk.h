@@ -56,6 +56,22 @@ struct FullKParams {
 #endif
 enum { FK_PLAIN = 0, FK_RESID = 1, FK_ROPE = 2, FK_PUB = 3 };
 
+// Launch head of gemm_fullk64_kernel (kernarg preload): what a K-slice wave needs before its first weight request is out -- the block's unit
+// (rowsplit, hd), the helper / K-wave split (nw = K-slice waves of the block), the weight and meta descriptors (qw, meta, KC, N_pad, NT, ilv) and the image (x, M).
+// These travel as the kernel's LEADING SCALAR parameters, which arrive in SGPRs at wave start (14 dwords: the whole preload budget next to the kernarg
+// segment pointer); a by-value struct is never preloaded, so the rest of FullKParams follows them unchanged and the kernel's first lines put the head back.
+// h_hd is a COPY of r.hd for the block's tile numbers only and is not put back: the epilogue reads r.hd with its neighbours, and a dead slot inside that run
+// made hipcc load the run wide over it at entry, reuse the dead register at once and wait for the load in front of the weight requests.
+#define FULLK_HEAD_PARAMS const void* h_qw, const uint32_t* h_meta, const f16* h_x, int h_M, int h_KC, int h_N_pad, int h_NT, int h_ilv, int h_rowsplit, int h_hd, int h_nw
+#define FULLK_HEAD_BIND(fp)                                                                                                              \
+    do { (fp).g.qw = h_qw; (fp).g.meta = h_meta; (fp).g.x = h_x; (fp).g.M = h_M; (fp).g.KC = h_KC; (fp).g.N_pad = h_N_pad; (fp).g.NT = h_NT; \
+         (fp).ilv = h_ilv; (fp).rowsplit = h_rowsplit; } while (0)
+// the one place that splits a filled FullKParams into head + rest
+template <class Kernel>
+inline void launch_fullk_head(Kernel k, dim3 grid, dim3 block, size_t lds, hipStream_t st, const FullKParams& fp, int nw) {
+    hipLaunchKernelGGL(k, grid, block, lds, st, fp.g.qw, fp.g.meta, fp.g.x, fp.g.M, fp.g.KC, fp.g.N_pad, fp.g.NT, fp.ilv, fp.rowsplit, fp.r.hd, nw, fp);
+}
+
 inline void set_kv_layout(RopeEpi& r, int layout, int hd, int page) {
     const bool kref = layout != MI355_KV_LAYOUT_NATIVE, vvec = layout == MI355_KV_LAYOUT_REF_VVEC;
     r.k_tok = kref ? 8 : hd;   r.k_chunk = kref ? page * 8 : 8;    // [page][hd]  |  [hd/8][page][8]

@@ -39,8 +39,10 @@ template <int TPB> struct Stage64<FK_ROPE, TPB>  { float cs[64][16 * TPB]; int p
 // between 0.5 and 7 us of a 10.5 us launch), and per 8 MFMAs a (4 tiles x 2 row blocks) block loads 2 fragments + 1 weight KB where a (2 x 4) block loads 4 + 0.5:
 // QKV at 64 rows 504 -> 336 wave-loads per CU on the same 144 blocks, O (4 tiles x 1 row block, 224 blocks) 280 -> 224.
 template <int WB, int GS, int MB, int EPI, int CPW, int RING, int TPB = 2>
-__global__ __launch_bounds__(1024) void gemm_fullk64_kernel(const FullKParams fp) {
+__global__ __launch_bounds__(1024) void gemm_fullk64_kernel(FULLK_HEAD_PARAMS, const FullKParams rest) {
     static_assert(TPB == 2 || TPB == 4, "tiles per block");
+    FullKParams fp = rest;                           // the launch head (gemm_fullk.h) arrives in SGPRs; everything below reads the struct as before
+    FULLK_HEAD_BIND(fp);
     constexpr bool W8 = WB == 8;                     // per-channel INT8 (GS is then a dummy 4)
     constexpr int LPC = WB / 4;                      // 1 KB wave-loads per (tile, chunk)
     constexpr int NSUB = 4 / GS, SPG = 4 / NSUB;     // GS: 4 -> g128, 2 -> g64, 1 -> g32: (zero, scale) words per chunk and column, k-steps per word
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(1024) void gemm_fullk64_kernel(const FullKParams fp
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int NW   = (int)(blockDim.x >> 6) - 1;     // K-slice waves; wave NW is the helper
+    const int NW   = h_nw;                           // K-slice waves, (blockDim.x >> 6) - 1 from the head: the helper / K-wave branch below waits for no load; wave NW is the helper
     const int jj = lane & 15, q = lane >> 4;
     Stage64<EPI, TPB>& sg = *reinterpret_cast<Stage64<EPI, TPB>*>(smem + (size_t)NW * TPB * MB * 1024);
     FK_STAMP(0);
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(1024) void gemm_fullk64_kernel(const FullKParams fp
     const int rb0 = part * MB;                       // first row block of this block (0 without a row split)
     int tile[TPB];
     if constexpr (EPI == FK_ROPE) {
-        const int hh = fp.r.hd >> 5;                 // tiles per half head (even: the TPB / 2 pairs of a block belong to one head)
+        const int hh = h_hd >> 5;                    // tiles per half head (even: the TPB / 2 pairs of a block belong to one head); fp.r.hd, from the launch head
 #pragma unroll
         for (int pp = 0; pp < TPB / 2; ++pp) {
             const int pair = unit * (TPB / 2) + pp, h = pair / hh, j = pair % hh;
@@ -386,7 +388,7 @@ int launch64_t(const FullKParams& fp, int blocks, hipStream_t st) {
     if (lds > 160 * 1024) return MI355_ERR_UNSUPPORTED;
     if (lds > 64 * 1024)
         if (int e = raise_dynamic_lds((const void*)k, "gemm_fullk64")) return e;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * (NW + 1)), lds, st, fp);
+    launch_fullk_head(k, dim3(blocks), dim3(64 * (NW + 1)), lds, st, fp, NW);
     MI355_CHECK_LAUNCH("gemm_fullk64_kernel");
     return MI355_OK;
 }

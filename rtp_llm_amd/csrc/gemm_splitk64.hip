@@ -31,6 +31,19 @@ struct SplitK64Params {
     int dbg;          // tuning build, timing only (same instruction stream): 1 no activation traffic, 2 no weight traffic
 };
 
+// Launch head (kernarg preload): what a wave needs before its first weight request is out -- the block's (column group, K split) and K slice
+// (xmap, cps, KC), the weight and meta descriptors (qw, meta, NT, N_pad, dbg) and the image (x, M) -- as the kernel's LEADING SCALAR parameters, which arrive
+// in SGPRs at wave start (13 dwords of the 14 next to the kernarg segment pointer); a by-value struct is never preloaded, so the whole SplitK64Params follows
+// them and the kernel's first lines put the head back.
+#define SPLITK64_HEAD_PARAMS const void* h_qw, const uint32_t* h_meta, const f16* h_x, int h_M, int h_KC, int h_N_pad, int h_NT, int h_cps, int h_xmap, int h_dbg
+#define SPLITK64_HEAD_BIND(sp) \
+    do { (sp).g.qw = h_qw; (sp).g.meta = h_meta; (sp).g.x = h_x; (sp).g.M = h_M; (sp).g.KC = h_KC; (sp).g.N_pad = h_N_pad; (sp).g.NT = h_NT; (sp).g.cps = h_cps; (sp).xmap = h_xmap; (sp).dbg = h_dbg; } while (0)
+// the one place that splits a filled SplitK64Params into head + rest
+template <class Kernel>
+inline void launch_splitk64_head(Kernel k, dim3 grid, dim3 block, size_t lds, hipStream_t st, const SplitK64Params& sp) {
+    hipLaunchKernelGGL(k, grid, block, lds, st, sp.g.qw, sp.g.meta, sp.g.x, sp.g.M, sp.g.KC, sp.g.N_pad, sp.g.NT, sp.g.cps, sp.xmap, sp.dbg, sp);
+}
+
 // Direct form (round 5, mi355_gemm_splitk64_direct): ONE K split and T = 2..5 tiles per block with the fused epilogue of the wide GEMM (bias / SiLU-mul,
 // row-major or image output) -- for a column-parallel SHARD under tensor parallelism (gate_up of Qwen2-7B at tp 2: 1184 tiles, Llama-3-70B at tp 8: 448), whose
 // N / tp columns leave the wide GEMM's 10-tiles-per-block form on half the chip (its phase structure needs >= 4 tiles per wave) and went through the staged
@@ -42,7 +55,9 @@ struct SplitK64Params {
 // DIRECT (round 6): the fused-epilogue store is an instance of its own -- with both stores behind a run-time `mode` the slab instances of the headline's
 // down_proj carried gemm_store's code and registers and measured 17.2 -> 17.6 us (profiles/r06_r04_vs_r05_same_box.txt).
 template <int WB, int GS, int MB, int T, int CPW, int RING, bool DIRECT = false, int UV = 0>   // UV: unit variant (2: the timing-only 9-VALU stream, tuning build)
-__global__ __launch_bounds__(512) void gemm_splitk64_kernel(const SplitK64Params sp) {
+__global__ __launch_bounds__(512) void gemm_splitk64_kernel(SPLITK64_HEAD_PARAMS, const SplitK64Params rest) {
+    SplitK64Params sp = rest;                            // the launch head arrives in SGPRs; everything below reads the struct as before
+    SPLITK64_HEAD_BIND(sp);
     const GemmParams& p = sp.g;
     constexpr int NW = 8;
     constexpr bool W8 = WB == 8;
@@ -211,8 +226,8 @@ int launch_splitk64_t(const SplitK64Params& sp, int G, hipStream_t st) {
     if (lds > 160 * 1024) return MI355_ERR_UNSUPPORTED;
     if (lds > 64 * 1024)
         if (int e = raise_dynamic_lds((const void*)k, "gemm_splitk64")) return e;
-    if (sp.xmap > 0) hipLaunchKernelGGL(k, dim3(G * sp.g.nsplit), dim3(512), lds, st, sp);
-    else             hipLaunchKernelGGL(k, dim3(G, sp.g.nsplit), dim3(512), lds, st, sp);
+    if (sp.xmap > 0) launch_splitk64_head(k, dim3(G * sp.g.nsplit), dim3(512), lds, st, sp);
+    else             launch_splitk64_head(k, dim3(G, sp.g.nsplit), dim3(512), lds, st, sp);
     MI355_CHECK_LAUNCH("gemm_splitk64_kernel");
     return MI355_OK;
 }
