@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MI355_ABI_VERSION 4
+#define MI355_ABI_VERSION 5
 
 typedef void* mi355_stream_t; /* hipStream_t */
 
@@ -46,6 +46,9 @@ enum {
 
 /* weight element kinds */
 enum { MI355_W4 = 4, MI355_W8 = 8, MI355_W16 = 16 };
+/* what the stored codes of a weight are (mi355_weight_t.wkind): integers with {zneg, scale} meta, or OCP FP8 e4m3 bit patterns
+ * with an fp32 scale per (128-row group, column) -- see "FP8 weights" at mi355_weight_t */
+enum { MI355_WKIND_INT = 0, MI355_WKIND_FP8_E4M3 = 1 };
 /* KV-cache element kinds (reference: KvCacheDataType, cpp/model_utils/AttentionConfig.h:9-12;
  * value 1 is the INT8 slot the reference removed, kept here) */
 enum { MI355_KV_FP16 = 0, MI355_KV_INT8 = 1, MI355_KV_BF16 = 2 };
@@ -87,6 +90,22 @@ const char* mi355_last_error(void);
  *   device_impl.py:252); AWQ: z_eff = z; symmetric autoquant: z_eff = 8 / 128.
  *   group_size 0 means one group spanning all of K (per-channel scale,
  *   reference a1: device_impl.py:183-192).
+ *
+ * FP8 weights (wkind = MI355_WKIND_FP8_E4M3; the block-quantised checkpoints of quant_method "fp8": e4m3 weights with one fp32
+ * weight_scale_inv per 128 x 128 block).  Requires wbits == MI355_W8 and group_size == 128, anything else is MI355_ERR_ARG.
+ *   `qweight` is the W8 tile image above, byte for byte the same addressing; the stored byte is the e4m3 bit pattern itself
+ *   (sign, 4 exponent bits of bias 7, 3 mantissa bits; no infinities; 0x7f / 0xff are NaN and must not occur), not an
+ *   offset-binary code.  Padding rows / columns hold code 0 (= +0.0).
+ *   `meta[g * N_pad + n]` is ONE fp32 in the 4-byte slot: the scale of (K-group g, column n); the checkpoint's 128 x 128 block scale
+ *   is expanded per column when packing (4 bytes per 128 weights, what W4 pays), padding columns hold scale 0.
+ *       W[k][n] = float(e4m3 byte) * scale[k / 128][n].
+ *   Numerics contract: the byte enters the MFMA as the exact 16-bit image of its e4m3 value (all 254 finite codes are exact in
+ *   fp16 and in bf16); products are accumulated in fp32 per 128-row group, and the fp32 scale multiplies that group's fp32 partial
+ *   sum on the accumulator side, at every M:  y += scale[g][n] * sum_{k in g} x[k] * e4m3(k, n).  There is no operand-side
+ *   fp16(scale * w) form and no activation-sum (zero point) term, so a scale that is subnormal or inexact in fp16 costs nothing.
+ *   Served by the staged decode kernels (mi355_linear_forward / _partial / _direct, M <= 8 fp16 also by the persistent kernel); every
+ *   fused / image launch and its *_ok / *_plan predicate refuses the kind (MI355_ERR_UNSUPPORTED / 0), the step driver then
+ *   composes the staged chain.
  * ---------------------------------------------------------------------- */
 typedef struct {
     const void* qweight; /* dev */
@@ -98,6 +117,7 @@ typedef struct {
     int32_t     N_pad;   /* multiple of 16 */
     int32_t     group_size; /* 32, 64, 128, or 0 = per-channel */
     int32_t     act_dtype;  /* MI355_ACT_F16 / MI355_ACT_BF16: dtype of x, bias, y (and of the elements of a W16 weight) */
+    int32_t     wkind;      /* MI355_WKIND_*: 0 = integer codes, so a zero-initialised struct keeps its meaning (sizeof stays 48) */
 } mi355_weight_t;
 
 /* epilogue flags for mi355_linear_forward */

@@ -21,7 +21,8 @@ KV_LAYOUT_NAMES = {"native": KV_LAYOUT_NATIVE, "ref": KV_LAYOUT_REF, "ref_vvec":
 EPI_NONE, EPI_SILU_MUL, EPI_OUT_F32, EPI_OUT_IMAGE = 0, 1, 2, 4
 PF_QKV, PF_O, PF_GATE_UP, PF_QKV_LATE, PF_O_LATE, PF_TP_COMM, PF_TP_INLAUNCH, PF_QKV_IN_FOLD = 1, 2, 4, 16, 32, 64, 128, 256   # mi355_decoder_set_weight_prefetch mask bits
 HINT_STAGED, HINT_NO_PERSISTENT = 0x100, 0x200
-ABI_VERSION = 4
+ABI_VERSION = 5
+WKIND_INT, WKIND_FP8_E4M3 = 0, 1   # mi355_weight_t.wkind
 LOGPROBS_MAX_TOP = 32
 KC_NAMES = ["gemm_quant", "gemm_lmhead", "attn", "rope_kv", "norm", "other", "comm"]
 
@@ -30,7 +31,7 @@ vp, i32, f32, sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
 
 class Weight(C.Structure):  # mi355_weight_t
     _fields_ = [("qweight", vp), ("meta", vp), ("wbits", i32), ("K", i32), ("N", i32),
-                ("K_pad", i32), ("N_pad", i32), ("group_size", i32), ("act_dtype", i32)]
+                ("K_pad", i32), ("N_pad", i32), ("group_size", i32), ("act_dtype", i32), ("wkind", i32)]
 
 
 class KVLayer(C.Structure):  # mi355_kv_layer_t

@@ -275,14 +275,14 @@ int plan_launches(mi355_decoder* d) {
     k.slab_qkv_img = k.slab_qkv;
     for (const auto& L : d->layers)
         k.slab_qkv_img = k.slab_qkv_img && L.qkv.K % 128 == 0 && L.qkv.K_pad == L.qkv.K &&
-                         mi355_gemm_splitk64_plan(64, L.qkv.N_pad / 16, L.qkv.K_pad / 128, L.qkv.wbits, L.qkv.group_size, kMaxSplits, nullptr) > 0;
+                         mi355_gemm_splitk64_plan(64, L.qkv.N_pad / 16, L.qkv.K_pad / 128, mi355_wfmt(&L.qkv), L.qkv.group_size, kMaxSplits, nullptr) > 0;
     // ... the post-attention RMSNorm deferred into gate_up's accumulators (mi355_deferred_norm_t): the O launch leaves gamma 2^-e h' as an image + the
     // per-tile sums of h'^2, the wide GEMM applies rsqrt(mean h'^2 + eps) 2^e: 6 launches per layer
     k.img_gate_up = k.img_o && c.hidden % 64 == 0 && TUNE(5) != 3;
     for (const auto& L : d->layers) k.img_gate_up = k.img_gate_up && mi355_gemm_wide_direct_ok(&L.gate_up);
     // ... and down_proj as 4 K-quarters from the image gate_up's SiLU epilogue writes (gemm_splitk64.hip) instead of 15 slabs
     auto quarters_ok = [](const mi355_weight_t& w) {
-        return w.K % 128 == 0 && w.K_pad == w.K && mi355_gemm_splitk64_plan(64, w.N_pad / 16, w.K_pad / 128, w.wbits, w.group_size, kMaxSplits, nullptr) > 0;
+        return w.K % 128 == 0 && w.K_pad == w.K && mi355_gemm_splitk64_plan(64, w.N_pad / 16, w.K_pad / 128, mi355_wfmt(&w), w.group_size, kMaxSplits, nullptr) > 0;
     };
     k.img_down = k.img_gate_up && c.inter % 32 == 0 && TUNE(5) != 4;
     for (const auto& L : d->layers) k.img_down = k.img_down && quarters_ok(L.down);
@@ -302,7 +302,7 @@ int plan_launches(mi355_decoder* d) {
     k.tp_img_gate = k.tp_img_down && c.hidden % 32 == 0 && TUNE(5) != 3;
     for (const auto& L : d->layers)
         k.tp_img_gate = k.tp_img_gate && L.gate_up.K % 128 == 0 && L.gate_up.K_pad == L.gate_up.K &&
-                        mi355_gemm_splitk64_direct_plan(64, L.gate_up.N_pad / 16, L.gate_up.K_pad / 128, L.gate_up.wbits, L.gate_up.group_size) > 0;
+                        mi355_gemm_splitk64_direct_plan(64, L.gate_up.N_pad / 16, L.gate_up.K_pad / 128, mi355_wfmt(&L.gate_up), L.gate_up.group_size) > 0;
     // the row-parallel O / down shards as ONE full-K launch each whose epilogue writes the rank's rows straight into the registered all-reduce buffer
     // (mi355_linear_publish_img), consumed by mi355_allreduce_fused_published_dt: no slabs, no fold + publish stage in front of the flag exchange
     k.tp_pub_o = k.tp_img_qkv && !(TUNE(8) & 1);
@@ -883,7 +883,7 @@ size_t linear_ws_bound(const mi355_model_config_t& c) {
     for (const auto& sh : shapes)
         for (int wbits : {4, 8, 16}) {
             mi355_weight_t w;
-            w.qweight = &need; w.meta = &need; w.wbits = wbits; w.K = sh[0]; w.N = sh[1]; w.act_dtype = c.act_dtype;   // bf16 plans other block shapes (and splits) above 32 rows
+            w.qweight = &need; w.meta = &need; w.wbits = wbits; w.wkind = MI355_WKIND_INT; w.K = sh[0]; w.N = sh[1]; w.act_dtype = c.act_dtype;   // bf16 plans other block shapes (and splits) above 32 rows
             w.K_pad = (sh[0] + 127) & ~127; w.N_pad = (sh[1] + 15) & ~15; w.group_size = wbits == 4 ? 128 : 0;
             need = std::max(need, mi355_linear_workspace_bytes(64, &w));
         }

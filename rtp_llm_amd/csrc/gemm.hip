@@ -69,14 +69,19 @@ namespace {
 // BF: bf16 activations (x, bias, y and, for WBITS = 16, the weights).  The W4 codes enter the bf16 MFMA as 128 + u and zero /
 // scale are applied on the accumulator side at EVERY row-block count (there is no packed bf16 arithmetic for an operand-side
 // dequant); the reference's bf16 linear is f16_linear.py:100-112 with a bf16 tensor.
-template <int WBITS, int MB, int NBW, int GS, int D, int NWN, int KG, bool BF = false>
+// F8: the bytes are FP8 e4m3 bit patterns (mi355_weight_t.wkind = MI355_WKIND_FP8_E4M3; WBITS = 8, GS = 4) and meta is one fp32 scale per
+// (group, column).  The byte is widened to the exact fp16 / bf16 image of its value (widen_fp8*, 4 VALU per 8 weights as widen_w8), a group's
+// products are summed in fp32 and the fp32 scale multiplies that sum on the accumulator side at EVERY row-block count: acc += scale * ag.
+// There is no zero point, so no sums of x (xsum) either.
+template <int WBITS, int MB, int NBW, int GS, int D, int NWN, int KG, bool BF = false, bool F8 = false>
 __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams p) {
+    static_assert(!F8 || (WBITS == 8 && GS == 4), "FP8 weights: 8-bit codes, 128-row groups");
     constexpr int LPC    = WBITS / 4;              // wave-loads per (tile, chunk)
     constexpr int NSUB   = (GS > 0) ? 4 / GS : 1;  // quantisation groups per chunk (per-channel: 1 pseudo group)
     constexpr int SPG    = 4 / NSUB;               // MFMA k-steps per group
     constexpr bool QUANT = WBITS != 16;
     constexpr bool GROUPED = GS > 0;               // per-group scale (else one scale per column, applied at the end)
-    constexpr bool CSIDE = QUANT && (MB <= 2 || BF); // zero/scale on the accumulator side (cheap for few row blocks);
+    constexpr bool CSIDE = QUANT && (MB <= 2 || BF || F8); // zero/scale on the accumulator side (cheap for few row blocks);
                                                    // MB >= 3: classic operand-side dequant, cost independent of MB
     constexpr int GT     = 64 * NWN;               // threads per k-group
     constexpr int XSLOTS = 256 * MB;               // 16-byte slots per x chunk tile
@@ -85,7 +90,8 @@ __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams
                                                    // vmcnt wait for x never drains newer weight loads
     constexpr int PPG    = 16 / NSUB;              // 16-byte pieces of a row per group
     __shared__ u32x4 xs[KG][2][XSLOTS];
-    __shared__ float xsum[CSIDE ? KG : 1][2][NSUB * 2][16 * MB];
+    constexpr bool XSUM = CSIDE && !F8;            // group sums of x for the zero-point term (FP8: none)
+    __shared__ float xsum[XSUM ? KG : 1][2][NSUB * 2][F8 ? 1 : 16 * MB];
     __shared__ f32x4 red[(KG > 1) ? NWN * NBW * MB * 64 : 1];
 
     const int tid  = threadIdx.x;
@@ -181,7 +187,7 @@ __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams
 #pragma unroll
         for (int u = 0; u < UPT; ++u) {
             if (UPT * GT == XSLOTS || xslot[u] >= 0) xs[kg][buf][xslot[u]] = xr[d][u];
-            if (CSIDE) {
+            if (XSUM) {
                 // group sums of x over the two code-bias classes; a row's 16 pieces sit in 16 adjacent lanes
                 const f16x2 ones = {(f16)1.f, (f16)1.f};
                 const u32x4 v = xr[d][u];
@@ -241,7 +247,8 @@ __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 float xb = 0.f;
-                if (CSIDE) {
+                XS[mb] = 0.f;
+                if (XSUM) {
                     const float x0 = xsum[kg][buf][gi * 2 + 0][mb * 16 + jj];
                     const float x1 = xsum[kg][buf][gi * 2 + 1][mb * 16 + jj];
                     XS[mb] = x0 + x1;
@@ -265,6 +272,10 @@ __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams
                         if (WBITS == 4) {
                             if (BF) a = widen_w4_bf16(wr[d][nb][0][s]);
                             else    a = __builtin_bit_cast(u32x4, widen_w4(wr[d][nb][0][s], w4c));
+                        } else if (F8) {
+                            const u32x4 w = wr[d][nb][(s >> 1) % LPC];
+                            if (BF) a = widen_fp8_bf16(w[(s & 1) * 2], w[(s & 1) * 2 + 1]);
+                            else    a = widen_fp8(w[(s & 1) * 2], w[(s & 1) * 2 + 1]);
                         } else {
                             const u32x4 w = wr[d][nb][(s >> 1) % LPC];
                             if (BF) a = widen_u8_bf16(w[(s & 1) * 2], w[(s & 1) * 2 + 1]);      // the stored byte itself: no code bias
@@ -294,6 +305,15 @@ __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams
             for (int nb = 0; nb < NBW; ++nb) {
                 if (!CSIDE) {
                     // operand-side path accumulated straight into acc
+                } else if (F8) {   // the fp32 scale of (group, column) times the group's fp32 partial sum
+                    float sc4[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        sc4[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((q * 4 + r) * 4, (int)mr[d][nb][gi]));
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) acc[nb][mb][r] = __builtin_fmaf(sc4[r], ag[nb][mb][r], acc[nb][mb][r]);
                 } else if (GROUPED) {
                     f16x2 m4[4];
 #pragma unroll
@@ -539,42 +559,42 @@ constexpr int kCfgBN[13] = {64, 128, 128, 256, 256, 64, 256, 256, 128, 128, 256,
 
 // Ring depths per shape: D1 for the M<=16 shapes, D2 for BN=128 (M<=32), DW for the 16-wave BN=256 shapes.
 // Bytes in flight per CU = waves * NBW * D KiB; ~85 KiB per CU are needed to cover HBM latency at 6 TB/s.
-template <int WBITS, int GS, int D1, int D2, int DW>
+template <int WBITS, int GS, int D1, int D2, int DW, bool F8 = false>
 int launch_gemm_t(const GemmParams& p, int cfg, hipStream_t st) {
     dim3 grid(cdiv(p.NT * 16, kCfgBN[cfg]), p.nsplit);
     if (cfg == 3) cfg = 4;   // (the three-row-block shapes 3 / 7 are gone: 33..48 rows run on the four-row-block ones)
     if (cfg == 7) cfg = 6;
     switch (cfg) {
-        case 0: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 2>), grid, dim3(512), 0, st, p); break;
-        case 1: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 2, GS, D1, 4, 2>), grid, dim3(512), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 2, 1, GS, D2, 8, 1>), grid, dim3(512), 0, st, p); break;
-        case 4: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 8, 1>), grid, dim3(512), 0, st, p); break;
-        case 5: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 1>), grid, dim3(256), 0, st, p); break;
-        case 6: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, 2, 16, 1>), grid, dim3(1024), 0, st, p); break;
-        case 8: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 8, 1>), grid, dim3(512), 0, st, p); break;
-        case 9: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 4, 1>), grid, dim3(256), 0, st, p); break;
-        case 10: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 4, GS, 2, 4, 1>), grid, dim3(256), 0, st, p); break;
-        case 11: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 10, 1>), grid, dim3(640), 0, st, p); break;
-        default: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 4, 1>), grid, dim3(256), 0, st, p); break;
+        case 0: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 2, false, F8>), grid, dim3(512), 0, st, p); break;
+        case 1: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 2, GS, D1, 4, 2, false, F8>), grid, dim3(512), 0, st, p); break;
+        case 2: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 2, 1, GS, D2, 8, 1, false, F8>), grid, dim3(512), 0, st, p); break;
+        case 4: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 8, 1, false, F8>), grid, dim3(512), 0, st, p); break;
+        case 5: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 1, false, F8>), grid, dim3(256), 0, st, p); break;
+        case 6: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, 2, 16, 1, false, F8>), grid, dim3(1024), 0, st, p); break;
+        case 8: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 8, 1, false, F8>), grid, dim3(512), 0, st, p); break;
+        case 9: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 4, 1, false, F8>), grid, dim3(256), 0, st, p); break;
+        case 10: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 4, GS, 2, 4, 1, false, F8>), grid, dim3(256), 0, st, p); break;
+        case 11: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 10, 1, false, F8>), grid, dim3(640), 0, st, p); break;
+        default: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 4, 1, false, F8>), grid, dim3(256), 0, st, p); break;
     }
     MI355_CHECK_LAUNCH("gemm_wq_kernel");
     return MI355_OK;
 }
 
 // bf16 activations: the three shapes the planner picks by row-block count (+ the narrow-N shape 8), nothing else instantiated
-template <int WBITS, int GS, int D1, int D2, int DW>
+template <int WBITS, int GS, int D1, int D2, int DW, bool F8 = false>
 int launch_gemm_bf16_t(const GemmParams& p, int cfg, hipStream_t st) {
     dim3 grid(cdiv(p.NT * 16, kCfgBN[cfg]), p.nsplit);
     switch (cfg) {
-        case 1: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 2, GS, D1, 4, 2, true>), grid, dim3(512), 0, st, p); break;
-        case 5: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 1, true>), grid, dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 2, 1, GS, D2, 8, 1, true>), grid, dim3(512), 0, st, p); break;
-        case 8: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 8, 1, true>), grid, dim3(512), 0, st, p); break;
-        case 6: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, 2, 16, 1, true>), grid, dim3(1024), 0, st, p); break;
+        case 1: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 2, GS, D1, 4, 2, true, F8>), grid, dim3(512), 0, st, p); break;
+        case 5: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 1, true, F8>), grid, dim3(256), 0, st, p); break;
+        case 2: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 2, 1, GS, D2, 8, 1, true, F8>), grid, dim3(512), 0, st, p); break;
+        case 8: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 8, 1, true, F8>), grid, dim3(512), 0, st, p); break;
+        case 6: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, 2, 16, 1, true, F8>), grid, dim3(1024), 0, st, p); break;
 #ifdef MI355_TUNING   // other shapes tried for the four-row-block bf16 case (tools/gemm_bench.py --bf16 1 --nbw N): all behind 6 / 8
-        case 9: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 4, 1, true>), grid, dim3(256), 0, st, p); break;
-        case 10: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 4, GS, 2, 4, 1, true>), grid, dim3(256), 0, st, p); break;
-        case 12: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 4, 1, true>), grid, dim3(256), 0, st, p); break;
+        case 9: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 4, 1, true, F8>), grid, dim3(256), 0, st, p); break;
+        case 10: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 4, GS, 2, 4, 1, true, F8>), grid, dim3(256), 0, st, p); break;
+        case 12: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 4, 1, true, F8>), grid, dim3(256), 0, st, p); break;
 #endif
         default: mi355_set_error("gemm (bf16): block shape %d not built", cfg); return MI355_ERR_UNSUPPORTED;
     }
@@ -582,7 +602,12 @@ int launch_gemm_bf16_t(const GemmParams& p, int cfg, hipStream_t st) {
     return MI355_OK;
 }
 
+// wbits: the format code of mi355_wfmt (internal.h): 4 / 8 / 16, or MI355_WFMT_FP8
 int launch_gemm(const GemmParams& p, int wbits, int group_size, int cfg, hipStream_t st) {
+    if (wbits == MI355_WFMT_FP8) {
+        if (group_size != 128) { mi355_set_error("gemm: FP8 weights need group_size 128 (got %d)", group_size); return MI355_ERR_UNSUPPORTED; }
+        return p.bf16 ? launch_gemm_bf16_t<8, 4, 4, 2, 2, true>(p, cfg, st) : launch_gemm_t<8, 4, 4, 2, 2, true>(p, cfg, st);
+    }
     if (p.bf16) {
         if (wbits == 16) return launch_gemm_bf16_t<16, 0, 2, 2, 2>(p, cfg, st);
         if (wbits == 4 && group_size == 128) return launch_gemm_bf16_t<4, 4, 4, 4, 4>(p, cfg, st);
@@ -620,6 +645,9 @@ int check_weight(const mi355_weight_t* w) {
     MI355_CHECK_ARG(w->wbits == 16 || w->meta, "linear: quantized weight needs meta");
     MI355_CHECK_ARG((uint64_t)w->K_pad * w->N_pad * w->wbits / 8 < 0xFFFFFFF0ull, "linear: weight image >= 4 GiB");
     MI355_CHECK_ARG(w->act_dtype == MI355_ACT_F16 || w->act_dtype == MI355_ACT_BF16, "linear: act_dtype=%d", w->act_dtype);
+    MI355_CHECK_ARG(w->wkind == MI355_WKIND_INT || w->wkind == MI355_WKIND_FP8_E4M3, "linear: wkind=%d", w->wkind);
+    MI355_CHECK_ARG(w->wkind != MI355_WKIND_FP8_E4M3 || (w->wbits == MI355_W8 && w->group_size == 128),
+                    "linear: FP8 e4m3 weights are wbits 8 with 128-row groups (got wbits=%d group_size=%d)", w->wbits, w->group_size);
     return MI355_OK;
 }
 
@@ -730,16 +758,16 @@ extern "C" int mi355_linear_partial(const void* x, int32_t M, const mi355_weight
     // it measured 3-8 % behind the staged kernel -- b=1 linears 1.55 vs 1.48 ms/step; tuning switch 4 = 2 re-enables it)
     const bool bf = p.bf16;    // bf16 activations: the staged kernel is the only family built for them
     if (!bf && M <= 8 && w->wbits != 16 && TUNE(4) == 2) {
-        const int rc = mi355_gemm_smallm(&p, w->wbits, w->group_size, 1, max_splits, stream);
+        const int rc = mi355_gemm_smallm(&p, mi355_wfmt(w), w->group_size, 1, max_splits, stream);
         if (rc != MI355_ERR_UNSUPPORTED) return rc;
     }
     if (!bf && M > 16 && w->wbits != 16 && TUNE(5) != 1) { // register-resident activations, K split over the waves (gemm_wide.hip)
-        const int rc = mi355_gemm_wide(&p, w->wbits, w->group_size, 1, max_splits, stream);
+        const int rc = mi355_gemm_wide(&p, mi355_wfmt(w), w->group_size, 1, max_splits, stream);
         if (rc != MI355_ERR_UNSUPPORTED) return rc;
     }
     const GemmPlan g = plan_gemm(M, w, max_splits);
     p.nsplit = g.nsplit; p.cps = g.cps;
-    if (int e = launch_gemm(p, w->wbits, w->group_size, g.cfg, (hipStream_t)stream)) return e;
+    if (int e = launch_gemm(p, mi355_wfmt(w), w->group_size, g.cfg, (hipStream_t)stream)) return e;
     return p.nsplit;
 }
 
@@ -767,7 +795,7 @@ extern "C" int mi355_linear_forward(const void* x, int32_t M, const mi355_weight
     if (!bf && M >= 128 && w->wbits != 16 && t_pf < t_slab) {
         GemmParams ps; fill_params(ps, x, M, w);
         ps.mode = mode; ps.bias = (const f16*)bias; ps.y = y; ps.ldy = ldy;
-        const int rc = mi355_gemm_prefill(&ps, w->wbits, w->group_size, stream);
+        const int rc = mi355_gemm_prefill(&ps, mi355_wfmt(w), w->group_size, stream);
         if (rc != MI355_ERR_UNSUPPORTED) return rc;
     }
     for (int m0 = 0; m0 < M; m0 += 64) {
@@ -777,7 +805,7 @@ extern "C" int mi355_linear_forward(const void* x, int32_t M, const mi355_weight
                                                              // reduce launch (stand-alone call: qkv 9.1 vs 14.6 us at M = 1)
             GemmParams ps; fill_params(ps, (const f16*)x + (size_t)m0 * w->K, Mc, w);
             ps.mode = mode; ps.bias = (const f16*)bias; ps.y = (char*)y + (size_t)m0 * ldy * ysz; ps.ldy = ldy;
-            const int rc = mi355_gemm_smallm(&ps, w->wbits, w->group_size, 0, 1, stream);
+            const int rc = mi355_gemm_smallm(&ps, mi355_wfmt(w), w->group_size, 0, 1, stream);
             if (rc >= 0) continue;
             if (rc != MI355_ERR_UNSUPPORTED) return rc;
         }
@@ -785,7 +813,7 @@ extern "C" int mi355_linear_forward(const void* x, int32_t M, const mi355_weight
             GemmParams ps; fill_params(ps, (const f16*)x + (size_t)m0 * w->K, Mc, w);
             ps.mode = mode; ps.bias = (const f16*)bias; ps.y = (char*)y + (size_t)m0 * ldy * ysz; ps.ldy = ldy;
             int rc = MI355_ERR_UNSUPPORTED;
-            if (rc == MI355_ERR_UNSUPPORTED) rc = mi355_gemm_wide(&ps, w->wbits, w->group_size, 0, 1, stream);
+            if (rc == MI355_ERR_UNSUPPORTED) rc = mi355_gemm_wide(&ps, mi355_wfmt(w), w->group_size, 0, 1, stream);
             if (rc >= 0) continue;
             if (rc != MI355_ERR_UNSUPPORTED) return rc;
         }
@@ -799,10 +827,10 @@ extern "C" int mi355_linear_forward(const void* x, int32_t M, const mi355_weight
         p.nsplit = ns; p.cps = cps; p.ldy = ldy;
         if (ns == 1) {
             p.mode = mode; p.bias = (const f16*)bias; p.y = yc;
-            if (int e = launch_gemm(p, w->wbits, w->group_size, g.cfg, st)) return e;
+            if (int e = launch_gemm(p, mi355_wfmt(w), w->group_size, g.cfg, st)) return e;
         } else {
             p.mode = MODE_PARTIAL; p.partials = (float*)workspace;
-            if (int e = launch_gemm(p, w->wbits, w->group_size, g.cfg, st)) return e;
+            if (int e = launch_gemm(p, mi355_wfmt(w), w->group_size, g.cfg, st)) return e;
             launch_reduce_epilogue((const float*)workspace, ns, Mc, w->N, w->N_pad, (const f16*)bias, yc, ldy, mode, bf, st);
             MI355_CHECK_LAUNCH("reduce_epilogue_kernel");
         }
@@ -830,13 +858,13 @@ extern "C" int mi355_linear_direct(const void* x, int32_t M, const mi355_weight_
         p.y_img = 1;
     }
     if (!bf && !out_img && M <= 8 && w->wbits != 16 && (TUNE(4) == 2 || TUNE(7) == 1)) {
-        const int rc = mi355_gemm_smallm(&p, w->wbits, w->group_size, 0, 1, stream);
+        const int rc = mi355_gemm_smallm(&p, mi355_wfmt(w), w->group_size, 0, 1, stream);
         if (rc >= 0) return MI355_OK;
         if (rc != MI355_ERR_UNSUPPORTED) return rc;
     }
     if (!bf && M > 16 && w->wbits != 16 && !(epilogue & MI355_HINT_STAGED) && TUNE(5) != 1) {
         int rc = MI355_ERR_UNSUPPORTED;
-        if (rc == MI355_ERR_UNSUPPORTED) rc = mi355_gemm_wide(&p, w->wbits, w->group_size, 0, 1, stream);
+        if (rc == MI355_ERR_UNSUPPORTED) rc = mi355_gemm_wide(&p, mi355_wfmt(w), w->group_size, 0, 1, stream);
         if (rc >= 0) return MI355_OK;
         if (rc != MI355_ERR_UNSUPPORTED) return rc;
     }
@@ -849,9 +877,9 @@ extern "C" int mi355_linear_direct(const void* x, int32_t M, const mi355_weight_
     }
     const GemmPlan g = plan_gemm(M, w, max_splits);
     p.nsplit = g.nsplit; p.cps = g.cps;
-    if (g.nsplit == 1) return launch_gemm(p, w->wbits, w->group_size, g.cfg, (hipStream_t)stream);
+    if (g.nsplit == 1) return launch_gemm(p, mi355_wfmt(w), w->group_size, g.cfg, (hipStream_t)stream);
     p.mode = MODE_PARTIAL; p.partials = (float*)workspace; p.bias = nullptr; p.y = nullptr;
-    if (int e = launch_gemm(p, w->wbits, w->group_size, g.cfg, (hipStream_t)stream)) return e;
+    if (int e = launch_gemm(p, mi355_wfmt(w), w->group_size, g.cfg, (hipStream_t)stream)) return e;
     launch_reduce_epilogue((const float*)workspace, g.nsplit, M, w->N, w->N_pad, (const f16*)bias, y, (mode == MODE_SILU) ? w->N / 2 : w->N, mode, bf,
                            (hipStream_t)stream, out_img ? cdiv(M, 16) : 0);
     MI355_CHECK_LAUNCH("reduce_epilogue_kernel");
@@ -861,6 +889,7 @@ extern "C" int mi355_linear_direct(const void* x, int32_t M, const mi355_weight_
 // ------------------------------------------------------------------ full-K kernels with fused consumers (gemm_fullk.hip)
 extern "C" int mi355_fullk_weight_ok(const mi355_weight_t* w) {
     if (w && w->act_dtype != MI355_ACT_F16) return 0;   // the full-K fused launches exist for fp16 activations only
+    if (w && w->wkind != MI355_WKIND_INT) return 0;     // integer codes only: an FP8 weight would be decoded as INT8
     const bool fmt = w && w->qweight && ((w->wbits == 4 && w->meta && (w->group_size == 128 || w->group_size == 64 || w->group_size == 32)) || w->wbits == 16);
     return fmt && w->K % 128 == 0 && w->K_pad == w->K && w->K_pad / 128 >= 4 && w->N % 16 == 0;
 }
@@ -868,6 +897,7 @@ extern "C" int mi355_fullk_weight_ok(const mi355_weight_t* w) {
 // the launches on activation images (gemm_fullk64 / gemm_splitk64 / gemm_wide image entries): W4 group-wise weights in the native
 // image; the activation dtype of the surrounding tensors is free (the image itself is fp16, see common.h)
 static bool img_weight_ok(const mi355_weight_t* w) {
+    if (w && w->wkind != MI355_WKIND_INT) return false;   // no FP8 instances of the image launches
     const bool fmt = w && w->qweight && w->meta && ((w->wbits == 4 && (w->group_size == 128 || w->group_size == 64 || w->group_size == 32)) ||
                                                     (w->wbits == 8 && w->group_size == 0));   // round 5: per-channel W8 (load-time INT8 autoquant)
     return fmt && w->K % 128 == 0 && w->K_pad == w->K && w->K_pad / 128 >= 4 && w->N % 16 == 0;
@@ -904,7 +934,7 @@ extern "C" int mi355_linear_residual(const void* x, int32_t M, const mi355_weigh
     if (M > 64 || !mi355_fullk_weight_ok(w)) return MI355_ERR_UNSUPPORTED;
     GemmParams p; fill_params(p, x, M, w);
     p.mode = MODE_F16; p.bias = (const f16*)bias; p.ldy = w->N;
-    return mi355_gemm_fullk_residual(&p, w->wbits, w->group_size, residual_in, residual_out, tile_sumsq_out, tile_sumsq_ld, stream);
+    return mi355_gemm_fullk_residual(&p, mi355_wfmt(w), w->group_size, residual_in, residual_out, tile_sumsq_out, tile_sumsq_ld, stream);
 }
 
 static int check_fused_norm(const mi355_fused_norm_t* n, int M, int K, const char* what) {
@@ -922,7 +952,7 @@ extern "C" int mi355_norm_linear(const void* h, int32_t M, const mi355_fused_nor
     GemmParams p; fill_params(p, h, M, w);
     p.mode = (epilogue & MI355_EPI_OUT_F32) ? MODE_F32 : (epilogue & MI355_EPI_SILU_MUL) ? MODE_SILU : MODE_F16;
     p.bias = (const f16*)bias; p.y = y; p.ldy = (p.mode == MODE_SILU) ? w->N / 2 : w->N;
-    return mi355_gemm_fullk(&p, w->wbits, w->group_size, norm, stream);
+    return mi355_gemm_fullk(&p, mi355_wfmt(w), w->group_size, norm, stream);
 }
 
 extern "C" int mi355_qkv_rope_kv_write(const void* x, int32_t M, const mi355_weight_t* wqkv, const void* qkv_bias,
@@ -940,7 +970,7 @@ extern "C" int mi355_qkv_rope_kv_write(const void* x, int32_t M, const mi355_wei
     if (M > (norm ? 16 : 64) || !mi355_fullk_weight_ok(wqkv) || rope_dim != kv->hd) return MI355_ERR_UNSUPPORTED;
     GemmParams p; fill_params(p, x, M, wqkv);
     p.mode = MODE_F16; p.bias = (const f16*)qkv_bias; p.ldy = wqkv->N;
-    return mi355_gemm_fullk_rope(&p, wqkv->wbits, wqkv->group_size, norm, cos_sin, max_pos, positions, block_table, max_blocks_per_seq,
+    return mi355_gemm_fullk_rope(&p, mi355_wfmt(wqkv), wqkv->group_size, norm, cos_sin, max_pos, positions, block_table, max_blocks_per_seq,
                                  q_len, nh, kv, q_out, oob_count, stream);
 }
 
@@ -955,7 +985,7 @@ extern "C" int mi355_linear_residual_img(const void* x_img, int32_t M, const mi3
     if (M < 1 || M > 64 || !img_weight_ok(w)) return MI355_ERR_UNSUPPORTED;
     GemmParams p; fill_params(p, x_img, M, w);
     p.mode = MODE_F16; p.bias = (const f16*)bias; p.ldy = w->N;
-    return mi355_gemm_fullk_residual_img(&p, w->wbits, w->group_size, residual_in, residual_out, tile_sumsq_out, tile_sumsq_ld, nullptr, 0.f, nullptr, stream);
+    return mi355_gemm_fullk_residual_img(&p, mi355_wfmt(w), w->group_size, residual_in, residual_out, tile_sumsq_out, tile_sumsq_ld, nullptr, 0.f, nullptr, stream);
 }
 
 // Tensor parallelism (round 6): the row-parallel shard of a 1-64-row step -- O behind the attention image, down behind the SiLU image -- as ONE full-K
@@ -979,7 +1009,7 @@ extern "C" int mi355_linear_publish_img(const void* x_img, int32_t M, const mi35
     if (int e = mi355_allreduce_publish_target(ar, M, w->N, &tgt)) return e;
     GemmParams p; fill_params(p, x_img, M, w);
     p.mode = MODE_F16; p.bias = (const f16*)bias; p.ldy = w->N;
-    return mi355_gemm_fullk_publish_img(&p, w->wbits, w->group_size, &tgt, stream);
+    return mi355_gemm_fullk_publish_img(&p, mi355_wfmt(w), w->group_size, &tgt, stream);
 }
 
 extern "C" int mi355_linear_residual_prenorm_img(const void* x_img, int32_t M, const mi355_weight_t* w, const void* bias, const void* residual_in,
@@ -992,7 +1022,7 @@ extern "C" int mi355_linear_residual_prenorm_img(const void* x_img, int32_t M, c
     if (M < 1 || M > 64 || !img_weight_ok(w)) return MI355_ERR_UNSUPPORTED;
     GemmParams p; fill_params(p, x_img, M, w);
     p.mode = MODE_F16; p.bias = (const f16*)bias; p.ldy = w->N;
-    return mi355_gemm_fullk_residual_img(&p, w->wbits, w->group_size, residual_in, residual_out, tile_sumsq_out, tile_sumsq_ld, norm_weight,
+    return mi355_gemm_fullk_residual_img(&p, mi355_wfmt(w), w->group_size, residual_in, residual_out, tile_sumsq_out, tile_sumsq_ld, norm_weight,
                                          ldexpf(1.f, -norm_exp), xg_img_out, stream);
 }
 
@@ -1013,7 +1043,7 @@ extern "C" int mi355_linear_deferred_norm_img(const void* xg_img, int32_t M, con
         MI355_CHECK_ARG(p.mode != MODE_F32 && p.ldy % 32 == 0, "linear_deferred_norm_img: an image output is a 16-bit tensor with a multiple of 32 columns");
         p.y_img = 1;
     }
-    return mi355_gemm_wide_img(&p, w->wbits, w->group_size, dn, stream);
+    return mi355_gemm_wide_img(&p, mi355_wfmt(w), w->group_size, dn, stream);
 }
 
 // y = epilogue(x W + bias) in ONE launch from an activation image, for a linear whose N does not fill the chip in the wide GEMM's form: a column-parallel
@@ -1032,7 +1062,7 @@ extern "C" int mi355_linear_direct_img(const void* x_img, int32_t M, const mi355
         MI355_CHECK_ARG(p.mode != MODE_F32 && p.ldy % 32 == 0, "linear_direct_img: an image output is a 16-bit tensor with a multiple of 32 columns");
         p.y_img = 1;
     }
-    return mi355_gemm_splitk64_direct(&p, w->wbits, w->group_size, stream);
+    return mi355_gemm_splitk64_direct(&p, mi355_wfmt(w), w->group_size, stream);
 }
 
 // Split-K slabs of a deep-K linear (down_proj) at 1-64 rows from an activation image (gemm_splitk64.hip): returns the number of
@@ -1044,7 +1074,7 @@ extern "C" int mi355_linear_partial_img(const void* x_img, int32_t M, const mi35
     if (M < 1 || M > 64 || !img_weight_ok(w)) return MI355_ERR_UNSUPPORTED;
     GemmParams p; fill_params(p, x_img, M, w);
     p.x_img = 1; p.x_bytes = (uint32_t)mi355_act_image_bytes(M, w->K); p.partials = partials;
-    return mi355_gemm_splitk64(&p, w->wbits, w->group_size, max_splits > 16 ? 16 : max_splits, stream);
+    return mi355_gemm_splitk64(&p, mi355_wfmt(w), w->group_size, max_splits > 16 ? 16 : max_splits, stream);
 }
 
 extern "C" int mi355_qkv_rope_kv_write_img(const void* x_img, int32_t M, const mi355_weight_t* wqkv, const void* qkv_bias,
@@ -1060,6 +1090,6 @@ extern "C" int mi355_qkv_rope_kv_write_img(const void* x_img, int32_t M, const m
     if (M < 1 || M > 64 || !img_weight_ok(wqkv) || rope_dim != kv->hd) return MI355_ERR_UNSUPPORTED;
     GemmParams p; fill_params(p, x_img, M, wqkv);
     p.mode = MODE_F16; p.bias = (const f16*)qkv_bias; p.ldy = wqkv->N;
-    return mi355_gemm_fullk_rope_img(&p, wqkv->wbits, wqkv->group_size, cos_sin, max_pos, positions, block_table, max_blocks_per_seq,
+    return mi355_gemm_fullk_rope_img(&p, mi355_wfmt(wqkv), wqkv->group_size, cos_sin, max_pos, positions, block_table, max_blocks_per_seq,
                                      q_len, nh, kv, q_out, oob_count, stream);
 }

@@ -246,6 +246,27 @@ __device__ __forceinline__ f16x8 widen_w8(uint32_t lo, uint32_t hi) {
     return __builtin_bit_cast(f16x8, r);
 }
 
+// FP8 e4m3 (OCP) bytes -> the exact fp16 / bf16 image of their values: every finite code is representable in both (3 mantissa bits;
+// smallest subnormal 2^-9, largest 448).  v_cvt_scalef32_pk_*_fp8 converts the two bytes of one word of the source (op_sel picks the
+// word) and multiplies by a scale operand, passed as 1.0: 4 VALU per 8 weights, the cost of widen_w8.  Builtins, not inline asm: the
+// compiler places the wait states between the conversion and the MFMA that reads it.
+__device__ __forceinline__ u32x4 widen_fp8(uint32_t lo, uint32_t hi) {
+    u32x4 r;
+    r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false));
+    r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true));
+    r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false));
+    r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true));
+    return r;
+}
+__device__ __forceinline__ u32x4 widen_fp8_bf16(uint32_t lo, uint32_t hi) {
+    u32x4 r;
+    r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false));
+    r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true));
+    r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false));
+    r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true));
+    return r;
+}
+
 // Operand-side dequant (M > 32): scale * (u - z) in fp16 — exact subtract of the biased code, one rounding.
 // Even code pairs come out as 1024+u, odd pairs as 64+u (see widen_w4), so the subtract uses two exact
 // constants -(1024+z) and -(64+z).  1 shift + 4 v_and_or + 4 v_pk_add + 4 v_pk_mul = 13 VALU per 8 weights.

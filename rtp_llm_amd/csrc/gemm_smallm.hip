@@ -26,8 +26,11 @@ struct SmallMParams {
     int tiles_max;
 };
 
-template <int WBITS, int GS, int D, int NW>
+// F8: FP8 e4m3 bytes with one fp32 scale per (128-row group, column) (mi355_weight_t.wkind; gemm.hip): the exact fp16 image of the byte into
+// the MFMA, acc += scale * (fp32 sum of the group); no zero point, so no indicator MFMAs.
+template <int WBITS, int GS, int D, int NW, bool F8 = false>
 __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams sp) {
+    static_assert(!F8 || (WBITS == 8 && GS == 4), "FP8 weights: 8-bit codes, 128-row groups");
     const GemmParams& p = sp.g;
     constexpr int LPC  = WBITS / 4;
     constexpr int NSUB = (GS > 0) ? 4 / GS : 1;
@@ -139,11 +142,14 @@ __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams
             for (int ss = 0; ss < SPG; ++ss) {
                 const int s = gi * SPG + ss;
                 const f16x8 b = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(smem + xbase + s * 64));
-                x0a = mfma16x16x32(ind0, b, x0a);
+                if (!F8) x0a = mfma16x16x32(ind0, b, x0a);
                 if (WBITS == 4) x1a = mfma16x16x32(ind1, b, x1a);
                 f16x8 a;
                 if (WBITS == 4) {
                     a = widen_w4(wr[d][0][s], w4c);
+                } else if (F8) {
+                    const u32x4 w = wr[d][(s >> 1) % LPC];
+                    a = __builtin_bit_cast(f16x8, widen_fp8(w[(s & 1) * 2], w[(s & 1) * 2 + 1]));
                 } else {
                     const u32x4 w = wr[d][(s >> 1) % LPC];
                     a = widen_w8(w[(s & 1) * 2], w[(s & 1) * 2 + 1]);
@@ -151,7 +157,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams
                 ag = mfma16x16x32(a, b, ag);
             }
             const float XS = x0a[0] + x1a[0], XB = 960.f * x1a[0];
-            if (GROUPED) {
+            if (F8) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(__builtin_bit_cast(float, mr[d][gi][r]), ag[r], acc[r]);
+            } else if (GROUPED) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const f16x2 m = as_h2(mr[d][gi][r]);
@@ -200,10 +209,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams
     }
 }
 
-template <int WBITS, int GS, int D = 4>
+template <int WBITS, int GS, int D = 4, bool F8 = false>
 int launch_t(const SmallMParams& sp, size_t lds, hipStream_t st) {
     constexpr int NW = 16;
-    auto k = gemm_smallm_kernel<WBITS, GS, D, NW>;
+    auto k = gemm_smallm_kernel<WBITS, GS, D, NW, F8>;
     if (int e = raise_dynamic_lds((const void*)k, "gemm_smallm")) return e; // allow > 64 KiB of dynamic LDS
     hipLaunchKernelGGL(k, dim3(sp.GT, sp.g.nsplit), dim3(64 * NW), lds, st, sp);
     MI355_CHECK_LAUNCH("gemm_smallm_kernel");
@@ -217,7 +226,9 @@ int launch_t(const SmallMParams& sp, size_t lds, hipStream_t st) {
 extern "C" int mi355_gemm_smallm(const void* gp, int wbits, int group_size, int want_partial, int max_splits,
                                  mi355_stream_t stream) {
     GemmParams g = *reinterpret_cast<const GemmParams*>(gp);
-    if (g.M > 8 || (wbits != 4 && wbits != 8)) return MI355_ERR_UNSUPPORTED;
+    const bool fp8 = wbits == MI355_WFMT_FP8;         // format code of mi355_wfmt (internal.h)
+    if (fp8 && (group_size != 128 || g.bf16)) return MI355_ERR_UNSUPPORTED;
+    if (g.M > 8 || (wbits != 4 && wbits != 8 && !fp8)) return MI355_ERR_UNSUPPORTED;
     if (wbits == 4 && !(group_size == 128 || group_size == 64 || group_size == 32)) return MI355_ERR_UNSUPPORTED;
     if (wbits == 8 && !(group_size == 0 || group_size == 128)) return MI355_ERR_UNSUPPORTED;
     constexpr int NW = 16, CUS = 256;
@@ -249,7 +260,8 @@ extern "C" int mi355_gemm_smallm(const void* gp, int wbits, int group_size, int 
 #ifdef MI355_TUNING
     if (wbits == 4 && group_size == 128 && TUNE(3) == 1) return (rc = launch_t<4, 4, 8>(sp, lds, st)) < 0 ? rc : g.nsplit;
 #endif
-    if (wbits == 4) rc = group_size == 128 ? launch_t<4, 4>(sp, lds, st) : group_size == 64 ? launch_t<4, 2>(sp, lds, st) : launch_t<4, 1>(sp, lds, st);
+    if (fp8)        rc = launch_t<8, 4, 4, true>(sp, lds, st);
+    else if (wbits == 4) rc = group_size == 128 ? launch_t<4, 4>(sp, lds, st) : group_size == 64 ? launch_t<4, 2>(sp, lds, st) : launch_t<4, 1>(sp, lds, st);
     else            rc = group_size == 0 ? launch_t<8, 0>(sp, lds, st) : launch_t<8, 4>(sp, lds, st);
     return rc < 0 ? rc : g.nsplit;
 }

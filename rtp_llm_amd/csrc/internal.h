@@ -19,6 +19,11 @@ static inline const char* mi355_kv_layout_problem(int32_t layout, int32_t kv_dty
             return MI355_ERR_ARG;                                                                                               \
         }                                                                                                                       \
     } while (0)
+/* Format code the GEMM launchers take in place of a bare mi355_weight_t.wbits (their `wbits` parameter): 4 / 8 / 16 for integer / 16-bit
+ * weights, MI355_WFMT_FP8 for wkind = MI355_WKIND_FP8_E4M3.  A launcher without an FP8 instance matches none of its integer cases on
+ * that code and returns MI355_ERR_UNSUPPORTED, so an FP8 image can never be decoded as INT8 g128 by falling through. */
+enum { MI355_WFMT_FP8 = 0x108 };
+static inline int mi355_wfmt(const mi355_weight_t* w) { return w->wkind == MI355_WKIND_FP8_E4M3 ? MI355_WFMT_FP8 : w->wbits; }
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -292,12 +292,12 @@ private:
 class Mi355WeightOnlyLinear {
 public:
     Mi355WeightOnlyLinear(torch::Tensor qweight, std::optional<torch::Tensor> meta, int64_t wbits, int64_t K, int64_t N,
-                          int64_t K_pad, int64_t N_pad, int64_t group_size, std::optional<torch::Tensor> bias):
+                          int64_t K_pad, int64_t N_pad, int64_t group_size, std::optional<torch::Tensor> bias, int64_t wkind):
         qweight_(std::move(qweight)), meta_(meta.value_or(torch::Tensor())), bias_(bias.value_or(torch::Tensor())) {
         TORCH_CHECK(qweight_.is_cuda() && qweight_.is_contiguous(), "qweight must be a contiguous GPU tensor");
         w_.qweight = qweight_.data_ptr();
         w_.meta    = meta_.defined() ? meta_.data_ptr() : nullptr;
-        w_.wbits = (int)wbits; w_.K = (int)K; w_.N = (int)N; w_.K_pad = (int)K_pad; w_.N_pad = (int)N_pad; w_.group_size = (int)group_size; w_.act_dtype = MI355_ACT_F16;
+        w_.wbits = (int)wbits; w_.K = (int)K; w_.N = (int)N; w_.K_pad = (int)K_pad; w_.N_pad = (int)N_pad; w_.group_size = (int)group_size; w_.act_dtype = MI355_ACT_F16; w_.wkind = (int)wkind;
         if (bias_.defined()) act_of(bias_, "bias");
     }
     torch::Tensor forward(const torch::Tensor& x, int64_t epilogue) {
@@ -440,9 +440,9 @@ void registerPyModuleOps(py::module& m) {
         .def("set_kv_layout", &Mi355PagedAttnDecodeOp::set_kv_layout, py::arg("layout"));
     py::class_<Mi355WeightOnlyLinear>(m, "Mi355WeightOnlyLinear")
         .def(py::init<torch::Tensor, std::optional<torch::Tensor>, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                      std::optional<torch::Tensor>>(),
+                      std::optional<torch::Tensor>, int64_t>(),
              py::arg("qweight"), py::arg("meta"), py::arg("wbits"), py::arg("K"), py::arg("N"), py::arg("K_pad"), py::arg("N_pad"),
-             py::arg("group_size"), py::arg("bias") = py::none())
+             py::arg("group_size"), py::arg("bias") = py::none(), py::arg("wkind") = 0)
         .def("forward", &Mi355WeightOnlyLinear::forward, py::arg("x"), py::arg("epilogue") = 0);
     m.def("rmsnorm", &rmsnorm, "RMSNorm", py::arg("output"), py::arg("input"), py::arg("weight"), py::arg("eps"), py::arg("hip_stream") = 0);
     m.def("fused_add_rmsnorm", &fused_add_rmsnorm, "residual add + RMSNorm", py::arg("output"), py::arg("residual_out"), py::arg("input"),

@@ -24,7 +24,7 @@ from .quant import PackedWeight
 @dataclass
 class QuantConfig:
     """Subset of rtp_llm/config/quant_config.py:281-300,641-685 that the decode path reads."""
-    method: str = "none"        # "none" | "int8" (load-time autoquant) | "gptq" | "awq"
+    method: str = "none"        # "none" | "int8" (load-time autoquant) | "gptq" | "awq" | "fp8" (e4m3, 128 x 128 block scales)
     bits: int = 16
     group_size: int = 0
 
@@ -144,6 +144,28 @@ class _W4A16Impl(_PackedImpl):
         self._finish_init(quant.pack_groupwise_w4(weight, weight_zeros, weight_scales, gs), bias)
 
 
+class _Fp8Impl(_PackedImpl):
+    """FP8 e4m3 weight-only with 128 x 128 block scales (the `quant_method: "fp8"` checkpoints), 16-bit activations.
+    weight float8_e4m3fn [K, N]; weight_scales fp32, either one scale per (128-row group, column) [ceil(K/128), N] or the
+    checkpoint's block scales [ceil(K/128), ceil(N/128)] (expanded per column here)."""
+
+    @classmethod
+    def can_handle(cls, quant_config, weight, weight_scales, hw_kernel_config=None, weight_scale_2=None, input_scale=None):
+        return weight_scales is not None and weight.dtype == torch.float8_e4m3fn and weight_scales.dim() == 2
+
+    def __init__(self, weight, weight_scales=None, input_scales=None, bias=None, quant_config=None, weight_scale_2=None):
+        super().__init__(weight, weight_scales, input_scales, bias, quant_config, weight_scale_2)
+        K, N = weight.shape
+        G = (K + quant.FP8_BLOCK - 1) // quant.FP8_BLOCK
+        if tuple(weight_scales.shape) == (G, N):
+            scales = weight_scales.float()
+        elif tuple(weight_scales.shape) == (G, (N + quant.FP8_BLOCK - 1) // quant.FP8_BLOCK):
+            scales = quant.expand_fp8_block_scales(weight_scales, N)
+        else:
+            raise ValueError(f"FP8: weight_scales {tuple(weight_scales.shape)} is neither [K/128, N] nor [K/128, N/128] for a [{K}, {N}] weight")
+        self._finish_init(quant.pack_fp8_block(weight.contiguous().view(torch.uint8), scales), bias)
+
+
 class Mi355F16Linear(_F16Impl, LinearBase):
     pass
 
@@ -156,7 +178,12 @@ class Mi355W4A16Linear(_W4A16Impl, LinearBase):
     pass
 
 
-STRATEGY_IMPLS = (("Mi355F16Linear", _F16Impl), ("Mi355W8A16Linear", _W8A16Impl), ("Mi355W4A16Linear", _W4A16Impl))
+class Mi355Fp8Linear(_Fp8Impl, LinearBase):
+    pass
+
+
+STRATEGY_IMPLS = (("Mi355F16Linear", _F16Impl), ("Mi355W8A16Linear", _W8A16Impl), ("Mi355W4A16Linear", _W4A16Impl),
+                  ("Mi355Fp8Linear", _Fp8Impl))
 
 
 class LinearFactory:
@@ -185,5 +212,5 @@ class LinearFactory:
                                  weights.get(zeros_key) if zeros_key else None)
 
 
-for _s in (Mi355F16Linear, Mi355W8A16Linear, Mi355W4A16Linear):
+for _s in (Mi355F16Linear, Mi355W8A16Linear, Mi355W4A16Linear, Mi355Fp8Linear):
     LinearFactory.register(_s)

@@ -7,6 +7,9 @@ The decode-path slice of the reference's loader stack:
   * GPTQ / AWQ tensors `.qweight/.qzeros/.scales` (model_loader/group_wise_quant_weight.py:35-301), canonicalised
     by rtp_llm_amd.quant (device_impl.py:148-171,242-300); like the reference loader, `g_idx` (act-order) is not
     supported — the reference never reads it (SURVEY 8f n2) — and a non-trivial g_idx is rejected here;
+  * FP8 block-quantised checkpoints (`quant_method: "fp8"`, the published form of the Qwen3 dense family): `.weight` float8_e4m3fn
+    [out, in] with `.weight_scale_inv` fp32 [ceil(out/128), ceil(in/128)]; the codes are kept as they are and the block scale is
+    expanded per output column (_linear_fp8), so splits and merges are plain column / 128-row operations;
   * `--quantization int8`: load-time per-channel autoquant of the fp16 linears (weight_only_quant_weight.py:94-105).
 
 With quantization="int8" the per-channel scales are computed on the full [K, N] weight BEFORE the row-parallel TP split
@@ -109,9 +112,13 @@ def _f16(t: torch.Tensor, name: str, dtype: torch.dtype = torch.float16) -> torc
     return o
 
 
-def _linear_fp16(sh: _Shards, prefix: str, dtype: torch.dtype = torch.float16) -> CanonLinear:
-    w = _f16(sh.get(prefix + ".weight"), prefix, dtype)    # HF stores [out, in]
+def _from_fp16_tensor(t: torch.Tensor, prefix: str, dtype: torch.dtype = torch.float16) -> CanonLinear:
+    w = _f16(t, prefix, dtype)                              # HF stores [out, in]
     return CanonLinear("fp16", w.shape[1], w.shape[0], w=w.t().contiguous())
+
+
+def _linear_fp16(sh: _Shards, prefix: str, dtype: torch.dtype = torch.float16) -> CanonLinear:
+    return _from_fp16_tensor(sh.get(prefix + ".weight"), prefix, dtype)
 
 
 def _linear_quant(sh: _Shards, prefix: str, method: str, group_size: int) -> CanonLinear:
@@ -125,10 +132,48 @@ def _linear_quant(sh: _Shards, prefix: str, method: str, group_size: int) -> Can
     return CanonLinear("w4", q.shape[0], q.shape[1], q=q, scales=sc, z_eff=z, group_size=group_size)
 
 
+def _check_fp8_config(q: dict) -> set:
+    """The FP8 scheme this decode path serves: e4m3 weights, dynamic activations (the weight-only path ignores them), one scale per
+    128 x 128 block.  Everything else is refused by the name of the field.  Returns modules_to_not_convert as a set of names."""
+    fmt = q.get("fmt", q.get("format"))
+    if fmt not in (None, "e4m3"):
+        raise NotImplementedError(f"quantization_config.fmt={fmt!r}: only e4m3 FP8 weights are on this decode path")
+    if q.get("activation_scheme", "dynamic") != "dynamic":
+        raise NotImplementedError(f"quantization_config.activation_scheme={q.get('activation_scheme')!r}: static activation scales are not supported")
+    wbs = q.get("weight_block_size")
+    if wbs is None:
+        raise NotImplementedError("quantization_config.weight_block_size is absent: per-tensor / per-channel FP8 scales are not supported (128 x 128 blocks only)")
+    if list(wbs) != [quant.FP8_BLOCK, quant.FP8_BLOCK]:
+        raise NotImplementedError(f"quantization_config.weight_block_size={wbs}: only [128, 128] is supported")
+    return set(q.get("modules_to_not_convert") or [])
+
+
+def _linear_fp8(sh: _Shards, prefix: str, w: torch.Tensor) -> CanonLinear:
+    """w: the module's `.weight` as read from the checkpoint, float8_e4m3fn [out, in]."""
+    if not sh.has(prefix + ".weight_scale_inv"):
+        raise NotImplementedError(f"{prefix}: FP8 weight without weight_scale_inv (per-tensor weight_scale checkpoints are not supported)")
+    s = sh.get(prefix + ".weight_scale_inv")
+    N, K = w.shape
+    B = quant.FP8_BLOCK
+    if s.dim() != 2 or tuple(s.shape) != ((N + B - 1) // B, (K + B - 1) // B):
+        raise NotImplementedError(f"{prefix}.weight_scale_inv: shape {tuple(s.shape)}, expected one scale per 128 x 128 block of [{N}, {K}]")
+    codes = w.view(torch.uint8).t().contiguous()            # [K, N]
+    if bool(((codes & 0x7F) == 0x7F).any()):
+        raise ValueError(f"{prefix}.weight holds an FP8 NaN code (byte & 0x7f == 0x7f)")
+    scales = quant.expand_fp8_block_scales(s.float().t().contiguous(), N)
+    return CanonLinear("fp8", K, N, q=codes, scales=scales, group_size=B)
+
+
+def _cat_same_kind(parts, what: str) -> CanonLinear:
+    if len({p.kind for p in parts}) != 1:
+        raise NotImplementedError(f"{what}: the merged projections are stored in different formats {[p.kind for p in parts]}")
+    return CanonLinear.cat_cols(parts)
+
+
 def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 1, rank: int = 0,
                        max_layers: Optional[int] = None, split_embedding: bool = False,
                        dtype: torch.dtype = torch.float16) -> Tuple[ModelConfig, Dict]:
-    """Read an HF Qwen2/Llama/Qwen3 checkpoint (fp16, GPTQ-4bit or AWQ-4bit) into the canonical weight dict of
+    """Read an HF Qwen2/Llama/Qwen3 checkpoint (fp16, GPTQ-4bit, AWQ-4bit or FP8 e4m3 with 128 x 128 block scales) into the canonical weight dict of
     rtp_llm_amd.model (per-rank tensors when tp > 1).  quantization="int8" autoquantises fp16 linears at load time.
     split_embedding (tp > 1): the embedding table comes back as this rank's [vocab, hidden / tp] column slice, the reference's TP
     layout (utils/model_weight.py:1490 sp_neg1) -- pair it with DecoderEngine.set_embedding_split(); default: replicated table
@@ -137,16 +182,29 @@ def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 
         raise NotImplementedError(f"load_hf_checkpoint: dtype {dtype} with quantization {quantization}")
     cfg_json = json.load(open(os.path.join(path, "config.json")))
     mc, qc = config_from_hf(cfg_json, os.path.basename(os.path.normpath(path)))
-    if qc["method"] not in ("none", "gptq", "awq") or (qc["method"] != "none" and qc["bits"] != 4):
-        raise NotImplementedError(f"quantization_config {qc} is outside the decode path of this build (4-bit GPTQ/AWQ only)")
+    fp8 = qc["method"] == "fp8"
+    fp8_skip = _check_fp8_config(cfg_json.get("quantization_config") or {}) if fp8 else set()
+    if fp8 and quantization == "int8":
+        raise NotImplementedError("load_hf_checkpoint: quantization='int8' on an FP8 checkpoint")
+    if not fp8 and (qc["method"] not in ("none", "gptq", "awq") or (qc["method"] != "none" and qc["bits"] != 4)):
+        raise NotImplementedError(f"quantization_config {qc} is outside the decode path of this build (4-bit GPTQ/AWQ, FP8 128 x 128 blocks)")
     if qc["desc_act"]:
         raise NotImplementedError("desc_act=True (act-order) GPTQ checkpoints are not supported (the reference ignores g_idx too)")
     sh = _Shards(path)
     pre = "model." if sh.has("model.embed_tokens.weight") else ""
     L = mc.num_layers if max_layers is None else min(mc.num_layers, max_layers)
-    quantised = qc["method"] != "none"
+    quantised = qc["method"] in ("gptq", "awq")
+
+    def not_converted(name):   # listed in modules_to_not_convert: by full name, without the "model." prefix, or by a trailing component
+        names = {name, name[len(pre):] if pre and name.startswith(pre) else name}
+        return any(n in fp8_skip or any(n.endswith("." + m) for m in fp8_skip) for n in names)
 
     def lin(name):
+        if fp8 and not not_converted(name):
+            w = sh.get(name + ".weight")                      # read once: a module stored 16-bit falls through to _linear_fp16
+            if w.dtype == torch.float8_e4m3fn:
+                return _linear_fp8(sh, name, w)
+            return _from_fp16_tensor(w, name, dtype)
         c = _linear_quant(sh, name, qc["method"], qc["group_size"]) if quantised and sh.has(name + ".qweight") else _linear_fp16(sh, name, dtype)
         if c.kind == "fp16" and quantization == "int8":
             q, s = quant.symmetric_quantize_int8(c.w)
@@ -169,12 +227,12 @@ def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 
         raise ValueError("config.json says model_type 'qwen3' but the checkpoint has no self_attn.q_norm / k_norm tensors")
     for i in range(L):
         p = f"{pre}layers.{i}."
-        qkv = CanonLinear.cat_cols([lin(p + "self_attn.q_proj"), lin(p + "self_attn.k_proj"), lin(p + "self_attn.v_proj")])
+        qkv = _cat_same_kind([lin(p + "self_attn.q_proj"), lin(p + "self_attn.k_proj"), lin(p + "self_attn.v_proj")], p + "self_attn qkv")
         b = [bias(p + "self_attn.q_proj"), bias(p + "self_attn.k_proj"), bias(p + "self_attn.v_proj")]
         has_bias = has_bias or b[0] is not None
         layer = {
             "qkv": qkv, "o": lin(p + "self_attn.o_proj"),
-            "gate_up": CanonLinear.cat_cols([lin(p + "mlp.gate_proj"), lin(p + "mlp.up_proj")]),
+            "gate_up": _cat_same_kind([lin(p + "mlp.gate_proj"), lin(p + "mlp.up_proj")], p + "mlp gate_up"),
             "down": lin(p + "mlp.down_proj"),
             "qkv_bias": torch.cat(b).contiguous() if b[0] is not None else None,
             "input_norm": _f16(sh.get(p + "input_layernorm.weight"), p + "input_layernorm", dtype),

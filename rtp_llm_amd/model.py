@@ -91,7 +91,8 @@ MODELS = {m.name: m for m in (QWEN2_7B, QWEN2_0_5B, LLAMA3_70B, QWEN2_72B, QWEN3
 # --------------------------------------------------------------------------- canonical weights
 @dataclass
 class CanonLinear:
-    """One linear layer before packing.  kind: 'fp16' | 'int8' | 'w4'."""
+    """One linear layer before packing.  kind: 'fp16' | 'int8' | 'w4' | 'fp8' (q = e4m3 bit patterns uint8 [K,N], scales = fp32
+    [ceil(K/128), N]: the checkpoint's 128 x 128 block scale expanded per column, group_size 128, no zeros)."""
     kind: str
     K: int
     N: int
@@ -109,7 +110,15 @@ class CanonLinear:
             return quant.pack_fp16(il(self.w).to(dtype))
         if self.kind == "int8":
             return quant.pack_int8_per_channel(il(self.q), il(self.scales))
+        if self.kind == "fp8":
+            return quant.pack_fp8_block(il(self.q), il(self.scales))
         return quant.pack_groupwise_w4(il(self.q), il(self.z_eff), il(self.scales), self.group_size)
+
+    def factory_weight(self) -> torch.Tensor:
+        """The weight tensor as LinearFactory.create_linear takes it: the strategies tell the formats apart by dtype."""
+        if self.kind == "fp16":
+            return self.w
+        return self.q.view(torch.float8_e4m3fn) if self.kind == "fp8" else self.q
 
     def cols(self, lo: int, hi: int) -> "CanonLinear":
         """Column (output) slice — column-parallel split (sp_head / ffn_sp_neg1, utils/model_weight.py:265-277,472-509)."""
@@ -119,11 +128,11 @@ class CanonLinear:
     def rows(self, lo: int, hi: int) -> "CanonLinear":
         """Row (input) slice — row-parallel split (sp_0 / ffn_sp_0, :234-250); group aligned."""
         s = lambda t: None if t is None else t[lo:hi].contiguous()
-        if self.kind == "w4":
+        if self.kind in ("w4", "fp8"):
             g = self.group_size
             assert lo % g == 0 and hi % g == 0, "row split must be aligned to the quantisation group (align_size = tp*g)"
             return CanonLinear(self.kind, hi - lo, self.N, None, s(self.q), self.scales[lo // g: hi // g].contiguous(),
-                               self.z_eff[lo // g: hi // g].contiguous(), g)
+                               None if self.z_eff is None else self.z_eff[lo // g: hi // g].contiguous(), g)
         return CanonLinear(self.kind, hi - lo, self.N, s(self.w), s(self.q), self.scales, None, 0)
 
     def pad_cols(self, n: int) -> "CanonLinear":
@@ -138,7 +147,7 @@ class CanonLinear:
         if n == 0:
             return self
         z = lambda t, k: None if t is None else torch.cat([t, torch.zeros(k, *t.shape[1:], dtype=t.dtype, device=t.device)], dim=0)
-        if self.kind == "w4":
+        if self.kind in ("w4", "fp8"):   # fp8: code 0 is +0.0, z_eff stays None
             assert n % self.group_size == 0
             return CanonLinear(self.kind, self.K + n, self.N, None, z(self.q, n), z(self.scales, n // self.group_size),
                                z(self.z_eff, n // self.group_size), self.group_size)
@@ -167,6 +176,10 @@ def synth_linear(K: int, N: int, kind: str, device, gen: torch.Generator, group_
             return CanonLinear("fp16", K, N, w=w)
         q, s = quant.symmetric_quantize_int8(w)
         return CanonLinear("int8", K, N, q=q, scales=s)
+    if kind == "fp8":   # the published block-quantised form of xavier fp16 weights (K a multiple of 128, as the checkpoints' are)
+        w = ((torch.rand(K, N, device=device, generator=gen) * 2 - 1) * a).half()
+        q, s = quant.quant_fp8_block(w)
+        return CanonLinear("fp8", K, N, q=q, scales=s, group_size=quant.FP8_BLOCK)
     G = K // group_size
     q = torch.randint(0, 16, (K, N), device=device, generator=gen, dtype=torch.uint8)
     flag = 1 if method == "gptq" else 0
@@ -353,7 +366,7 @@ class CausalAttention(nn.Module):
 
     def __init__(self, layer: Dict, cfg: Optional[ModelConfig] = None):
         super().__init__()
-        mk = lambda c, bias=None: LinearFactory.create_linear(c.w if c.kind == "fp16" else c.q, bias, c.scales, None, c.z_eff)
+        mk = lambda c, bias=None: LinearFactory.create_linear(c.factory_weight(), bias, c.scales, None, c.z_eff)
         self.qkv_proj, self.o_proj = mk(layer["qkv"], layer["qkv_bias"]), mk(layer["o"])
         self.qk_norm = None
         if layer.get("q_norm") is not None:
@@ -374,7 +387,7 @@ class DenseMLP(nn.Module):
 
     def __init__(self, layer: Dict):
         super().__init__()
-        mk = lambda c: LinearFactory.create_linear(c.w if c.kind == "fp16" else c.q, None, c.scales, None, c.z_eff)
+        mk = lambda c: LinearFactory.create_linear(c.factory_weight(), None, c.scales, None, c.z_eff)
         self.gate_up_proj, self.down_proj, self.act = mk(layer["gate_up"]), mk(layer["down"]), FusedSiluAndMul()
 
     def forward(self, x):

@@ -44,7 +44,7 @@ def weight_struct(w: PackedWeight, act: torch.dtype = torch.float16) -> _C.Weigh
     if w.wbits == 16 and w.qweight.dtype != act:
         raise _C.Mi355Error(f"linear: 16-bit weight image is {w.qweight.dtype}, activations are {act}")
     return _C.Weight(w.qweight.data_ptr(), 0 if w.meta is None else w.meta.data_ptr(), w.wbits, w.K, w.N,
-                     w.K_pad, w.N_pad, w.group_size, _C.ACT_BF16 if act == torch.bfloat16 else _C.ACT_F16)
+                     w.K_pad, w.N_pad, w.group_size, _C.ACT_BF16 if act == torch.bfloat16 else _C.ACT_F16, w.wkind)
 
 
 def kv_struct(kv_base: torch.Tensor, scale_base: Optional[torch.Tensor], page: int, nkv: int, hd: int,

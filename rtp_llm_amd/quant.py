@@ -162,10 +162,11 @@ class PackedWeight:
     K_pad: int
     N_pad: int
     group_size: int                 # 0 = per-channel
+    wkind: int = 0                  # MI355_WKIND_*: 0 integer codes, 1 FP8 e4m3 bytes with an fp32 scale plane
 
     def to(self, device):
         return PackedWeight(self.qweight.to(device), None if self.meta is None else self.meta.to(device),
-                            self.wbits, self.K, self.N, self.K_pad, self.N_pad, self.group_size)
+                            self.wbits, self.K, self.N, self.K_pad, self.N_pad, self.group_size, self.wkind)
 
     @property
     def nbytes(self) -> int:
@@ -206,6 +207,57 @@ def pack_int8_per_channel(q: torch.Tensor, scale: torch.Tensor) -> PackedWeight:
 def pack_fp16(w: torch.Tensor) -> PackedWeight:
     K, N = w.shape
     return PackedWeight(pack_w16(w), None, 16, K, N, _ceil_to(K, 128), _ceil_to(N, 16), 0)
+
+
+# --------------------------------------------------------------------------- FP8 e4m3, 128 x 128 block scales
+FP8_BLOCK = 128
+FP8_E4M3_MAX = 448.0
+WKIND_INT, WKIND_FP8_E4M3 = 0, 1
+
+
+def expand_fp8_block_scales(block_scales: torch.Tensor, N: int) -> torch.Tensor:
+    """[ceil(K/128), ceil(N/128)] block scales -> [ceil(K/128), N]: one scale per (K-group, column), the form the kernels read."""
+    assert block_scales.dim() == 2 and block_scales.shape[1] == (N + FP8_BLOCK - 1) // FP8_BLOCK
+    return block_scales.float().repeat_interleave(FP8_BLOCK, dim=1)[:, :N].contiguous()
+
+
+def quant_fp8_block(w: torch.Tensor):
+    """[K, N] -> (codes uint8 [K, N] e4m3 bit patterns, scales fp32 [ceil(K/128), N]): per 128 x 128 block scale = amax / 448
+    (1 where the block is all zero), w / scale cast to float8_e4m3fn (round to nearest even).  For synthetic weights and tests;
+    the scale is expanded per column like a checkpoint's weight_scale_inv at load time."""
+    K, N = w.shape
+    KB, NB = (K + FP8_BLOCK - 1) // FP8_BLOCK, (N + FP8_BLOCK - 1) // FP8_BLOCK
+    wp = torch.zeros(KB * FP8_BLOCK, NB * FP8_BLOCK, dtype=torch.float32, device=w.device)
+    wp[:K, :N] = w.float()
+    amax = wp.reshape(KB, FP8_BLOCK, NB, FP8_BLOCK).abs().amax(dim=(1, 3))
+    bs = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    full = bs.repeat_interleave(FP8_BLOCK, dim=0).repeat_interleave(FP8_BLOCK, dim=1)[:K, :N]
+    codes = (w.float() / full).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.contiguous(), expand_fp8_block_scales(bs, N)
+
+
+def dequant_fp8(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """codes uint8 [K, N], scales fp32 [ceil(K/128), N] -> fp32 [K, N] = float(e4m3) * scale[k // 128]."""
+    K = codes.shape[0]
+    return codes.view(torch.float8_e4m3fn).float() * scales.float().repeat_interleave(FP8_BLOCK, dim=0)[:K]
+
+
+def pack_fp8_block(codes: torch.Tensor, scales: torch.Tensor) -> PackedWeight:
+    """codes uint8 [K, N] (e4m3 bit patterns), scales fp32 [ceil(K/128), N] -> the W8 tile image of the raw bytes plus an fp32
+    meta plane [K_pad/128, N_pad] (include/mi355_decode.h, "FP8 weights").  K is padded with code 0, N with code 0 and scale 0."""
+    assert codes.dtype == torch.uint8 and codes.dim() == 2
+    K, N = codes.shape
+    K_pad, N_pad = _ceil_to(K, 128), _ceil_to(N, 16)
+    G = K_pad // FP8_BLOCK
+    assert tuple(scales.shape) == (G, N), f"scales {tuple(scales.shape)} != ({G}, {N})"
+    if bool(((codes & 0x7F) == 0x7F).any()):
+        raise ValueError("FP8 e4m3 weight holds a NaN code (byte & 0x7f == 0x7f)")
+    u = _pad2(codes, K_pad, N_pad, 0)
+    KC, NT = K_pad // 128, N_pad // 16
+    x = u.reshape(KC, 2, 2, 4, 8, NT, 16).permute(5, 0, 1, 3, 6, 2, 4)   # as pack_w8: [nt, c, p, qq, i, h, e]
+    meta = torch.zeros(G, N_pad, dtype=torch.float32, device=codes.device)
+    meta[:, :N] = scales.float()
+    return PackedWeight(x.reshape(-1).contiguous(), meta.view(torch.int32).contiguous(), 8, K, N, K_pad, N_pad, FP8_BLOCK, WKIND_FP8_E4M3)
 
 
 def autoquant_int8(weight_kn: torch.Tensor) -> PackedWeight:

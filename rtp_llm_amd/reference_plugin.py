@@ -18,10 +18,12 @@ def make_strategies(ref_linear_base) -> List[type]:
     return [type(name, (impl, ref_linear_base), {"__module__": __name__, "__doc__": impl.__doc__}) for name, impl in STRATEGY_IMPLS]
 
 
-def register(ref_linear_factory, ref_linear_base, replace_f16: bool = False) -> List[type]:
+def register(ref_linear_factory, ref_linear_base, replace_f16: bool = False, replace_fp8: bool = False) -> List[type]:
     """Register the strategies with the reference's factory.  The fp16 strategy overlaps the reference's own ROCm fp16
     strategies (RocmF16Linear*), and the factory demands a unique match, so it is only registered when asked to replace
-    them (``replace_f16``: existing fp16 strategies are removed first)."""
+    them (``replace_f16``: existing fp16 strategies are removed first).  The same holds for the FP8 block-scale strategy and
+    the reference's ROCm FP8 strategies (``replace_fp8``: strategies that claim a float8_e4m3fn weight with 2-D block scales
+    are removed first); by default the FP8 slot is left to the reference."""
     out = []
     for cls in make_strategies(ref_linear_base):
         if cls.__name__ == "Mi355F16Linear":
@@ -31,6 +33,13 @@ def register(ref_linear_factory, ref_linear_base, replace_f16: bool = False) -> 
             probe = torch.zeros(8, 8, dtype=torch.float16)
             ref_linear_factory._strategies[:] = [s for s in ref_linear_factory._strategies
                                                  if not _safe_can_handle(s, probe)]
+        if cls.__name__ == "Mi355Fp8Linear":
+            if not replace_fp8:
+                continue
+            import torch
+            probe, scales = torch.zeros(128, 128, dtype=torch.float8_e4m3fn), torch.ones(1, 1, dtype=torch.float32)
+            ref_linear_factory._strategies[:] = [s for s in ref_linear_factory._strategies
+                                                 if not _safe_can_handle(s, probe, scales)]
         ref_linear_factory.register(cls)
         out.append(cls)
     return out
@@ -50,8 +59,8 @@ def register_attention(decode_list: list, prefill_list: list, fmha_base) -> List
     return out
 
 
-def _safe_can_handle(strategy, weight) -> bool:
+def _safe_can_handle(strategy, weight, weight_scales=None) -> bool:
     try:
-        return bool(strategy.can_handle(None, weight, None, None, None, None))
-    except Exception:  # noqa: BLE001  (a strategy that cannot even inspect an fp16 weight does not claim it)
+        return bool(strategy.can_handle(None, weight, weight_scales, None, None, None))
+    except Exception:  # noqa: BLE001  (a strategy that cannot even inspect the probe weight does not claim it)
         return False
