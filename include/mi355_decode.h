@@ -570,6 +570,16 @@ int                mi355_allreduce_set_spin_timeout_ms(mi355_allreduce_t* ar, in
  * .reshape(m, -1)).  Same transport, same graph-capture rules as the all-reduce; T * n * world * 2 <= max_bytes; out != x. */
 int mi355_allgather_hidden(mi355_allreduce_t* ar, const void* x_f16, void* out_f16, int32_t T, int32_t n, mi355_stream_t stream);
 
+/* out[B, V_local * world] = the ranks' fp32 [B, V_local] logits slices side by side, out[b][r V_local + j] = local_r[b][j], bit for bit (NaN payloads
+ * and infinities included): the logits gather of a vocab-split lm_head (rtp_llm/cpp/models/PyWrappedModel.cc:915-936) over the same transport,
+ * capturable, nothing synchronises.  local: row stride ld >= V_local, ld % 4 == 0; both buffers 16-byte aligned, out != local.  The rank's dense
+ * slice travels in 4096-byte units owned by block (unit % grid) of the launch, so the registered-buffer invariant (one owner block per location
+ * whatever the geometry) holds and these calls alternate freely with the other calls of a context.  One launch moves up to max_bytes of the
+ * slice; a larger slice takes ceil(B * V_local * 4 / max_bytes) launches, each with its own epoch -- a number fixed by (B, V_local, context), so
+ * a captured graph stays valid.  V_local % 4 != 0: MI355_ERR_UNSUPPORTED (16-byte transfers); a context of max_bytes < 4096: MI355_ERR_ARG.  All
+ * three hand-over forms give the same bits (under the granule protocol the gather uses the flag form, as mi355_allgather_hidden does). */
+int mi355_allgather_logits(mi355_allreduce_t* ar, const float* local, int32_t ld, float* out, int32_t B, int32_t V_local, mi355_stream_t stream);
+
 /* out[T,H] = sum over ranks of x[T,H] (fp16).  out may alias x. */
 int mi355_allreduce_sum(mi355_allreduce_t* ar, const void* x_f16, void* out_f16, int32_t T, int32_t H, mi355_stream_t stream);
 
@@ -745,7 +755,7 @@ int    mi355_decoder_set_qk_norm(mi355_decoder_t* d, const void* const* q_norm, 
  * is MI355_ERR_ARG.  The launch plan does not change with it: the same launches, other addresses. */
 int    mi355_decoder_set_kv_layout(mi355_decoder_t* d, int32_t layout);
 
-/* Sampled decoding inside the step (tp_size == 1): with a sampling config set, the tail of mi355_decoder_finish(d, 1, ...) after
+/* Sampled decoding inside the step: with a sampling config set, the tail of mi355_decoder_finish(d, 1, ...) after
  * mi355_decoder_begin, of mi355_decoder_step for every B <= max_batch and of what mi355_decoder_capture records becomes
  *   1. mi355_apply_penalties_history over history / history_len, when any penalty pointer is set: IN PLACE on bufs.logits, which
  *      then holds the penalised logits;
@@ -757,8 +767,9 @@ int    mi355_decoder_set_kv_layout(mi355_decoder_t* d, int32_t layout);
  * entries (history: [max_batch][history_ld]) owned by the caller, read when the launches run: the host may rewrite them between
  * steps and replays.  seed is required; temperature / top_k / top_p / the penalties may be NULL; history and history_len are
  * required with a penalty.  workspace: mi355_decoder_sampling_workspace_bytes(cfg) bytes, 256-byte aligned.  After
- * mi355_decoder_begin_rows with q_len > 1 (verify rows) the tail stays greedy.  tp_size > 1: MI355_ERR_UNSUPPORTED (the lm_head is
- * split over the vocabulary).  s == NULL: back to the greedy tail.  Legal whenever no step is in flight; drops captured graphs. */
+ * mi355_decoder_begin_rows with q_len > 1 (verify rows) the tail stays greedy.  tp_size > 1: only with the buffer of
+ * mi355_decoder_set_gathered_logits (without it MI355_ERR_UNSUPPORTED: the lm_head is split over the vocabulary) -- the tail then runs on the
+ * gathered rows, V = tp_size * vocab, and every rank must hold identical parameter and history arrays.  s == NULL: back to the greedy tail.  Legal whenever no step is in flight; drops captured graphs. */
 typedef struct {
     const float* temperature; const int32_t* top_k; const float* top_p; const uint64_t* seed;
     const float* repetition_penalty; const float* presence_penalty; const float* frequency_penalty;
@@ -768,7 +779,7 @@ typedef struct {
 size_t mi355_decoder_sampling_workspace_bytes(const mi355_model_config_t* cfg);
 int    mi355_decoder_set_sampling(mi355_decoder_t* d, const mi355_sampling_t* s);
 
-/* Log-probabilities inside the step (tp_size == 1): with a config set, the tail of every decode step (q_len == 1; eager, captured
+/* Log-probabilities inside the step: with a config set, the tail of every decode step (q_len == 1; eager, captured
  * or replayed) runs the two launches of mi355_logprobs on bufs.logits behind the choice of the token --
  *   greedy tail:  arg-max, then the log-probabilities of the unscaled logits (temperature NULL);
  *   sampled tail: penalties, mi355_sample_logits, then the log-probabilities under the sampling config's temperature of the
@@ -782,8 +793,8 @@ int    mi355_decoder_set_sampling(mi355_decoder_t* d, const mi355_sampling_t* s)
  * between steps and replays of the same graph (count = 0 records from column 0 again).  top_n in [0, MI355_LOGPROBS_MAX_TOP];
  * top_ids / top_logprobs are required with top_n > 0; token_logprobs, count and log_ld >= 1 always.  workspace:
  * mi355_decoder_logprobs_workspace_bytes(cfg, top_n) bytes, 256-byte aligned.  Independent of mi355_decoder_set_sampling, in either
- * order.  Verify rows (mi355_decoder_begin_rows with q_len > 1) record nothing.  tp_size > 1: MI355_ERR_UNSUPPORTED (the lm_head is
- * split over the vocabulary).  lp == NULL: off -- the step is launch for launch what it is without the feature.  Legal whenever no
+ * order.  Verify rows (mi355_decoder_begin_rows with q_len > 1) record nothing.  tp_size > 1: only with the buffer of
+ * mi355_decoder_set_gathered_logits (without it MI355_ERR_UNSUPPORTED: the lm_head is split over the vocabulary).  lp == NULL: off -- the step is launch for launch what it is without the feature.  Legal whenever no
  * step is in flight; drops captured graphs. */
 typedef struct {
     int32_t  top_n, log_ld;           /* alternatives per token; steps recorded per slot */
@@ -796,6 +807,26 @@ typedef struct {
 } mi355_logprobs_t;
 size_t mi355_decoder_logprobs_workspace_bytes(const mi355_model_config_t* cfg, int32_t top_n);
 int    mi355_decoder_set_logprobs(mi355_decoder_t* d, const mi355_logprobs_t* lp);
+
+/* Sampled decoding and log-probabilities under tensor parallelism (tp_size > 1).  The lm_head is split over the vocabulary, so the tail of a
+ * decode step first gathers the ranks' fp32 logits (the reference gathers them too, PyWrappedModel.cc:915-936) into a caller-owned buffer:
+ *   buf    address-stable, 256-byte aligned, mi355_decoder_gathered_logits_bytes(cfg) bytes (0 at tp_size 1): first the gathered rows
+ *          [max_batch][tp_size * vocab] fp32, then the staging [tp_size][max_batch][vocab] an external transport's all_gather writes.
+ * With the buffer set, mi355_decoder_set_sampling / _set_logprobs are accepted at tp_size > 1 (after an attach call whose vocab_offset is
+ * rank * vocab, with vocab_full == tp_size * vocab; otherwise MI355_ERR_ARG / MI355_ERR_UNSUPPORTED), and their workspace functions size
+ * themselves for tp_size * vocab columns whenever tp_size > 1.  The tail of a decode step (q_len == 1) with either config active becomes
+ *   attach_allreduce:  mi355_allgather_logits from bufs.logits into buf (counted per launch under MI355_KC_COMM);
+ *   attach_collective: all_gather of the contiguous [B][vocab] block into the staging, then one reorder launch into buf;
+ *   then the tail of tp_size 1 on the gathered rows, V = ld = tp_size * vocab: penalties in place on buf (bufs.logits keeps the rank's raw
+ *   slice), the fused sampler, the log-probability launches, the feedback.  Greedy with log-probabilities takes the arg-max of the gathered row
+ *   (lowest global index on ties: the id of the cross-rank arg-max).  The sampler works on integer masses and Philox counters keyed by the
+ *   position, so ranks holding the same parameter and history arrays draw the same token from the same gathered bits: nothing else crosses.
+ * Verify rows (q_len > 1) gather nothing and stay greedy; with the buffer set but no config active the step is launch for launch what it is
+ * without it; the step stays one linear chain on one stream.
+ * buf == NULL: off (MI355_ERR_ARG while a sampling / logprobs config is active).  tp_size == 1: MI355_ERR_ARG.  Too few bytes:
+ * MI355_ERR_WORKSPACE.  Legal whenever no step is in flight; drops captured graphs. */
+size_t mi355_decoder_gathered_logits_bytes(const mi355_model_config_t* cfg);
+int    mi355_decoder_set_gathered_logits(mi355_decoder_t* d, float* buf, size_t bytes);
 
 /* hipGraph: capture one full step for batch B on an internal stream, then replay
  * `nsteps` times back-to-back on `stream` (greedy feedback stays on device). */
@@ -874,7 +905,7 @@ enum {
     MI355_KC_ROPE_KV    = 3,
     MI355_KC_NORM       = 4,
     MI355_KC_OTHER      = 5,
-    MI355_KC_COMM       = 6, /* fused all-reduce launches (tp_size > 1) */
+    MI355_KC_COMM       = 6, /* fused all-reduce launches, the launches of the logits gather (tp_size > 1) */
     MI355_KC_COUNT      = 7
 };
 int mi355_decoder_profile(mi355_decoder_t* d, int32_t B, int32_t nsteps, float* out_ms,

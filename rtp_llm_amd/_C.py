@@ -166,6 +166,9 @@ SIGNATURES = {
     "mi355_decoder_set_weight_prefetch": (i32, [vp, i32]),
     "mi355_allreduce_set_prefetch": (i32, [vp, vp, sz]),
     "mi355_allgather_hidden": (i32, [vp, vp, vp, i32, i32, vp]),
+    "mi355_allgather_logits": (i32, [vp, vp, i32, vp, i32, i32, vp]),
+    "mi355_decoder_gathered_logits_bytes": (sz, [C.POINTER(ModelConfig)]),
+    "mi355_decoder_set_gathered_logits": (i32, [vp, vp, sz]),
     "mi355_decoder_workspace_bytes": (sz, [C.POINTER(ModelConfig)]),
     "mi355_decoder_create": (vp, [C.POINTER(ModelConfig), C.POINTER(LayerWeights), C.POINTER(ModelWeights), C.POINTER(StepBuffers)]),
     "mi355_decoder_destroy": (None, [vp]),

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
+#include <algorithm>
 #include <new>
 
 #include "common.h"
@@ -402,6 +403,75 @@ __global__ __launch_bounds__(256) void allgather_hidden_kernel(const GatherParam
     if (tid == 0) ar.epoch[b] = epoch;
 }
 
+// All-gather along the VOCABULARY dimension of the fp32 logits of a vocab-split lm_head (PyWrappedModel.cc:915-936 gathers [B, V / tp] fp32 per
+// rank): out[b][r V_local + j] = local_r[b][j], bit for bit -- the rows the sampler and the log-probability recorder of the step then run on.
+// A vocabulary row (up to 152064 fp32: ~600 KB) is far larger than a block's slot, so the row cannot be the ownership unit as in
+// allgather_hidden_kernel: the rank's dense [B][V_local] slice is cut into UNITS of kUnitBytes, unit u of a launch belongs to block u % grid and
+// sits at u / grid units inside that block's slot -- every location keeps its one owner block whatever (B, V_local) is, so these calls alternate
+// freely with the all-reduce, hidden-gather and arg-max calls of a context.  Only the rank's own slice is published: peers read it from its owner.
+// A launch moves at most max_bytes of the slice (the host issues several, each with its own epoch); V_local % 4 == 0 keeps a 16-byte vector inside
+// one row.
+constexpr int kUnitBytes = 4096;           // 256 threads x 16 bytes
+constexpr int kUnitVecs  = kUnitBytes / 16;
+struct LogitsGatherParams {
+    ArDev        ar;
+    const float* local;    // [B][ld], V_local valid columns
+    float*       out;      // [B][V_local * world]
+    int          ld, V_local;
+    uint32_t     vec0;     // first 16-byte vector of the dense slice this launch moves
+    uint32_t     nvec;     // ... and how many
+};
+
+__global__ __launch_bounds__(256) void allgather_logits_kernel(const LogitsGatherParams p) {
+    const ArDev& ar = p.ar;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const uint32_t epoch = ar.epoch[b] + 1;
+    const size_t par = (epoch & 1) * ar.parity_elems;
+    const __amdgpu_buffer_rsrc_t mine_rs = my_rsrc(ar);
+    const uint32_t nunits = (p.nvec + kUnitVecs - 1) / kUnitVecs;
+    const size_t Vf = (size_t)p.V_local * ar.world;
+    // publish this rank's units; its own columns of out come straight from the local rows
+    for (uint32_t u = b; u < nunits; u += gridDim.x) {
+        const uint32_t v = u * kUnitVecs + tid;
+        if (v >= p.nvec) continue;
+        const size_t e = (size_t)(p.vec0 + v) * 4;
+        const size_t row = e / p.V_local, col = e % p.V_local;
+        const u32x4 x = *reinterpret_cast<const u32x4*>(p.local + row * p.ld + col);
+        publish16(ar, mine_rs, par + (size_t)b * ar.slot_elems + (size_t)(u / gridDim.x) * (kUnitBytes / 2) + (size_t)tid * 8, x);
+        *reinterpret_cast<u32x4*>(p.out + row * Vf + (size_t)ar.rank * p.V_local + col) = x;
+    }
+    peer_barrier(ar, b, epoch);
+    __amdgpu_buffer_rsrc_t rp[kMaxWorld];
+#pragma unroll
+    for (int r = 0; r < kMaxWorld; ++r)
+        rp[r] = __builtin_amdgcn_make_buffer_rsrc((void*)ar.peer_data[r < ar.world ? r : 0], 0, ar.data_bytes, 0x00020000u);
+    for (uint32_t u = b; u < nunits; u += gridDim.x) {
+        const uint32_t v = u * kUnitVecs + tid;
+        if (v >= p.nvec) continue;
+        const size_t e = (size_t)(p.vec0 + v) * 4;
+        const size_t row = e / p.V_local, col = e % p.V_local;
+        const uint32_t off = (uint32_t)((par + (size_t)b * ar.slot_elems + (size_t)(u / gridDim.x) * (kUnitBytes / 2) + (size_t)tid * 8) * 2);
+        u32x4 in[kMaxWorld];
+#pragma unroll
+        for (int r = 0; r < kMaxWorld; ++r)
+            if (r < ar.world && r != ar.rank) in[r] = load_sys(rp[r], off);      // all peers in flight together
+#pragma unroll
+        for (int r = 0; r < kMaxWorld; ++r)
+            if (r < ar.world && r != ar.rank) *reinterpret_cast<u32x4*>(p.out + row * Vf + (size_t)r * p.V_local + col) = in[r];
+    }
+    __syncthreads();
+    if (tid == 0) ar.epoch[b] = epoch;
+}
+
+// [world][B][V] (what an external transport's all_gather leaves) -> [B][world * V]: the rows of allgather_logits_kernel
+__global__ __launch_bounds__(256) void interleave_logits_kernel(const float* __restrict__ staged, float* __restrict__ out, int world, int B, int V) {
+    const size_t n4 = (size_t)world * B * V / 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const size_t e = i * 4, col = e % V, rb = e / V, row = rb % B, r = rb / B;
+        *reinterpret_cast<u32x4*>(out + row * ((size_t)world * V) + r * V + col) = *reinterpret_cast<const u32x4*>(staged + e);
+    }
+}
+
 // Greedy argmax across a vocab-split lm_head: every rank publishes (best local logit, global index) per row, then picks
 // the overall best -- highest value, lowest global index on ties (torch.argmax semantics on the gathered row).
 struct ArgmaxParams {
@@ -776,6 +846,63 @@ extern "C" int mi355_allgather_hidden(mi355_allreduce_t* a, const void* x_f16, v
     MI355_CHECK_ARG((size_t)cdiv(T, grid) * n * a->world * 2 <= a->slot_bytes, "allgather: rows per block exceed the %zu-byte slot", a->slot_bytes);
     hipLaunchKernelGGL(allgather_hidden_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     MI355_CHECK_LAUNCH("allgather_hidden_kernel");
+    return MI355_OK;
+}
+
+// How many launches mi355_allgather_logits issues for a [B][V_local] slice on this context: one moves up to max_bytes (whole units).  Depends on
+// (B, V_local, context) only, so a captured graph holds the same launches every replay.  < 0: refused (message set).
+extern "C" int mi355_allgather_logits_launches(mi355_allreduce_t* a, int32_t B, int32_t V_local) {
+    MI355_CHECK_ARG(a && a->ready, "allgather_logits: context not opened (mi355_allreduce_open)");
+    MI355_CHECK_ARG(B > 0 && V_local > 0, "allgather_logits: B=%d V_local=%d", B, V_local);
+    if (V_local % 4 != 0) { mi355_set_error("allgather_logits: V_local=%d is not a multiple of 4 (16-byte transfers)", V_local); return MI355_ERR_UNSUPPORTED; }
+    MI355_CHECK_ARG(a->max_bytes >= (size_t)kUnitBytes, "allgather_logits: the context holds %zu bytes per call, one unit needs %d", a->max_bytes, kUnitBytes);
+    MI355_CHECK_ARG((size_t)B * V_local < ((size_t)1 << 32), "allgather_logits: B=%d x V_local=%d too large", B, V_local);
+    const size_t units = ((size_t)B * V_local * 4 + kUnitBytes - 1) / kUnitBytes, per = a->max_bytes / kUnitBytes;
+    return (int)((units + per - 1) / per);
+}
+
+// launch `part` (0 .. mi355_allgather_logits_launches - 1) of the gather: the step driver runs and profiles them one by one
+extern "C" int mi355_allgather_logits_part(mi355_allreduce_t* a, const float* local, int32_t ld, float* out, int32_t B, int32_t V_local,
+                                           int32_t part, mi355_stream_t stream) {
+    const int n = mi355_allgather_logits_launches(a, B, V_local);
+    if (n < 0) return n;
+    MI355_CHECK_ARG(local && out && (const void*)local != (const void*)out && (((uintptr_t)local | (uintptr_t)out) & 15) == 0,
+                    "allgather_logits: null, aliased or unaligned (16 bytes) buffers");
+    MI355_CHECK_ARG(ld >= V_local && ld % 4 == 0 && part >= 0 && part < n, "allgather_logits: ld=%d (>= V_local=%d, %% 4 == 0) part=%d of %d", ld, V_local, part, n);
+    const size_t nvec = (size_t)B * V_local / 4, per = a->max_bytes / kUnitBytes * kUnitVecs;     // vectors of the slice, of one launch
+    LogitsGatherParams p;
+    p.ar = dev_view(a);
+    p.local = local; p.out = out; p.ld = ld; p.V_local = V_local;
+    p.vec0 = (uint32_t)(per * part);
+    p.nvec = (uint32_t)std::min(per, nvec - per * part);
+    const int units = (int)((p.nvec + kUnitVecs - 1) / kUnitVecs);
+    const int grid = units < kMaxBlocks ? units : kMaxBlocks;
+    // units per block x unit <= max_bytes / kMaxBlocks + one unit <= the slot (mi355_allreduce_create); checked, not assumed
+    MI355_CHECK_ARG((size_t)cdiv(units, grid) * kUnitBytes <= a->slot_bytes, "allgather_logits: %d units per block exceed the %zu-byte slot", cdiv(units, grid), a->slot_bytes);
+    hipLaunchKernelGGL(allgather_logits_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    MI355_CHECK_LAUNCH("allgather_logits_kernel");
+    return MI355_OK;
+}
+
+extern "C" int mi355_allgather_logits(mi355_allreduce_t* a, const float* local, int32_t ld, float* out, int32_t B, int32_t V_local,
+                                      mi355_stream_t stream) {
+    const int n = mi355_allgather_logits_launches(a, B, V_local);
+    if (n < 0) return n;
+    for (int part = 0; part < n; ++part)
+        if (int e = mi355_allgather_logits_part(a, local, ld, out, B, V_local, part, stream)) return e;
+    return MI355_OK;
+}
+
+extern "C" int mi355_allreduce_rank(const mi355_allreduce_t* a) { return a ? a->rank : -1; }
+
+// [world][B][V] fp32 -> [B][world * V] (the tail of an external transport's all_gather of the logits)
+extern "C" int mi355_interleave_logits(const float* staged, float* out, int32_t world, int32_t B, int32_t V, mi355_stream_t stream) {
+    MI355_CHECK_ARG(staged && out && world > 0 && B > 0 && V > 0 && V % 4 == 0 && (((uintptr_t)staged | (uintptr_t)out) & 15) == 0,
+                    "interleave_logits: world=%d B=%d V=%d (V %% 4 == 0, 16-byte aligned buffers)", world, B, V);
+    const size_t n4 = (size_t)world * B * V / 4;
+    const int grid = (int)std::min<size_t>((n4 + 255) / 256, 1024);
+    hipLaunchKernelGGL(interleave_logits_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, staged, out, world, B, V);
+    MI355_CHECK_LAUNCH("interleave_logits_kernel");
     return MI355_OK;
 }
 

@@ -133,6 +133,10 @@ struct mi355_decoder {
     // log-probabilities of the chosen tokens (mi355_decoder_set_logprobs): two more launches behind the choice, recorded per slot
     bool             logprobs_on;
     mi355_logprobs_t logprobs;
+    // tp_size > 1 (mi355_decoder_set_gathered_logits): the vocabulary-gathered fp32 rows [max_batch][tp_size * vocab] the sampled tail and the
+    // log-probability recorder run on, then the staging [tp_size][max_batch][vocab] of an external transport's all_gather; null = off
+    float*           gathered;
+    float*           gather_stage;
     // graphs
     hipStream_t                    cap_stream;
     std::map<int, hipGraphExec_t>  graphs;
@@ -404,6 +408,7 @@ extern "C" mi355_decoder_t* mi355_decoder_create(const mi355_model_config_t* cfg
     d->started = false;
     d->sampling_on = false; d->penalty_ws = nullptr; d->sample_ws = nullptr; d->sample_ws_bytes = 0;
     d->logprobs_on = false;
+    d->gathered = nullptr; d->gather_stage = nullptr;
     d->kv_layout = MI355_KV_LAYOUT_NATIVE;
     d->B = 0; d->q_len = 1; d->cap_stream = nullptr; d->prof_on = false; d->ev_used = 0; d->ar = nullptr; d->vocab_offset = 0;
     d->has_ext = false; d->pairs_local = d->pairs_all = nullptr;
@@ -636,6 +641,11 @@ extern "C" int mi355_decoder_attach_allreduce(mi355_decoder_t* d, mi355_allreduc
     if (!d || !ar || d->cfg.tp_size <= 1 || vocab_offset < 0) {
         mi355_set_error("decoder_attach_allreduce: needs a decoder created with tp_size > 1 and an opened context"); return MI355_ERR_ARG;
     }
+    if ((d->sampling_on || d->logprobs_on) && vocab_offset != mi355_allreduce_rank(ar) * d->cfg.vocab) {
+        mi355_set_error("decoder_attach_allreduce: a sampling / logprobs config is active: vocab_offset must be rank * vocab = %d, %d given",
+                        mi355_allreduce_rank(ar) * d->cfg.vocab, vocab_offset);
+        return MI355_ERR_ARG;
+    }
     drop_graphs(d);   // graphs captured for the segmented path are stale now
     d->ar = ar; d->vocab_offset = vocab_offset;
     if (!d->side_stream) d->overlap = side_ready(d);
@@ -649,6 +659,11 @@ extern "C" int mi355_decoder_attach_collective(mi355_decoder_t* d, const mi355_c
         mi355_set_error("decoder_attach_collective: needs a decoder created with tp_size > 1 and a transport of that world size"); return MI355_ERR_ARG;
     }
     if (d->ar) { mi355_set_error("decoder_attach_collective: an all-reduce context is already attached"); return MI355_ERR_ARG; }
+    if ((d->sampling_on || d->logprobs_on) && vocab_offset != coll->rank * d->cfg.vocab) {
+        mi355_set_error("decoder_attach_collective: a sampling / logprobs config is active: vocab_offset must be rank * vocab = %d, %d given",
+                        coll->rank * d->cfg.vocab, vocab_offset);
+        return MI355_ERR_ARG;
+    }
     drop_graphs(d);
     if (!d->pairs_local) {
         const size_t one = align256((size_t)d->cfg.max_batch * 8);
@@ -993,13 +1008,13 @@ int ext_argmax(mi355_decoder* d, int B, hipStream_t st) {
     RUN(MI355_KC_OTHER, mi355_argmax_pick(d->pairs_all, d->ext.world, B, d->bufs.token_ids, d->bufs.positions, st));
     return MI355_OK;
 }
-// log-probabilities of the ids in token_ids under the logits in bufs.logits, recorded per slot (mi355_decoder_set_logprobs): the two
+// log-probabilities of the ids in token_ids under B rows of `logits` (V columns, dense), recorded per slot (mi355_decoder_set_logprobs): the two
 // launches of logprobs.hip, nothing without a config or on verify rows
-int logprob_tail(mi355_decoder* d, int B, int q_len, const float* temperature, hipStream_t st) {
+int logprob_tail(mi355_decoder* d, const float* logits, int V, int B, int q_len, const float* temperature, hipStream_t st) {
     if (!d->logprobs_on || q_len != 1) return MI355_OK;
-    const auto& c = d->cfg; const mi355_logprobs_t& lp = d->logprobs;
-    RUN(MI355_KC_OTHER, mi355_logprobs_segments(d->bufs.logits, B, c.vocab, c.vocab, temperature, lp.top_n, lp.workspace, lp.workspace_bytes, st));
-    RUN(MI355_KC_OTHER, mi355_logprobs_rows(d->bufs.logits, B, c.vocab, c.vocab, temperature, d->bufs.token_ids, lp.top_n, lp.token_logprobs, nullptr,
+    const mi355_logprobs_t& lp = d->logprobs;
+    RUN(MI355_KC_OTHER, mi355_logprobs_segments(logits, B, V, V, temperature, lp.top_n, lp.workspace, lp.workspace_bytes, st));
+    RUN(MI355_KC_OTHER, mi355_logprobs_rows(logits, B, V, V, temperature, d->bufs.token_ids, lp.top_n, lp.token_logprobs, nullptr,
                                             lp.top_ids, lp.top_logprobs, lp.top_n, lp.log_ld, lp.count, lp.cum_log_probs, lp.workspace,
                                             lp.workspace_bytes, st));
     return MI355_OK;
@@ -1012,39 +1027,108 @@ int greedy_tail(mi355_decoder* d, int B, int q_len, hipStream_t st) {
                                                   d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
     else if (d->has_ext) return ext_argmax(d, B, st);
     else RUN(MI355_KC_OTHER, mi355_argmax_ex(d->bufs.logits, B, c.vocab, c.vocab, d->bufs.token_ids, d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
-    return logprob_tail(d, B, q_len, nullptr, st);
+    return logprob_tail(d, d->bufs.logits, c.vocab, B, q_len, nullptr, st);
 }
-// sampled ids of B rows of logits -> token_ids, positions + 1 and the history (mi355_decoder_set_sampling; tp_size == 1).  The
-// penalties act in place: bufs.logits holds the penalised logits afterwards.  The token drawn here sits at position positions + 1.
-int sampled_tail(mi355_decoder* d, int B, hipStream_t st) {
-    const auto& c = d->cfg; const mi355_sampling_t& s = d->sampling;
+// sampled ids of B rows of `logits` (V columns, dense) -> token_ids, positions + 1 and the history (mi355_decoder_set_sampling).  The
+// penalties act in place: the rows hold the penalised logits afterwards.  The token drawn here sits at position positions + 1.
+int sampled_tail(mi355_decoder* d, float* logits, int V, int B, hipStream_t st) {
+    const mi355_sampling_t& s = d->sampling;
     if (s.repetition_penalty || s.presence_penalty || s.frequency_penalty)
-        RUN(MI355_KC_OTHER, mi355_apply_penalties_history(d->bufs.logits, B, c.vocab, c.vocab, s.repetition_penalty, s.presence_penalty,
+        RUN(MI355_KC_OTHER, mi355_apply_penalties_history(logits, B, V, V, s.repetition_penalty, s.presence_penalty,
                                                           s.frequency_penalty, s.history, s.history_ld, s.history_len, d->penalty_ws, st));
-    RUN(MI355_KC_OTHER, mi355_sample_logits_ex(d->bufs.logits, B, c.vocab, c.vocab, s.temperature, s.top_k, s.top_p, nullptr, s.seed,
+    RUN(MI355_KC_OTHER, mi355_sample_logits_ex(logits, B, V, V, s.temperature, s.top_k, s.top_p, nullptr, s.seed,
                                                d->bufs.positions, 1, d->bufs.token_ids, nullptr, nullptr, 0, d->sample_ws, d->sample_ws_bytes, st));
-    if (int e = logprob_tail(d, B, 1, s.temperature, st)) return e;
+    if (int e = logprob_tail(d, logits, V, B, 1, s.temperature, st)) return e;
     RUN(MI355_KC_OTHER, mi355_sample_feedback(d->bufs.token_ids, B, d->bufs.positions, s.history, s.history_len, s.history_ld, st));
     return MI355_OK;
 }
-int step_tail(mi355_decoder* d, int B, int q_len, hipStream_t st) {
-    return d->sampling_on && q_len == 1 ? sampled_tail(d, B, st) : greedy_tail(d, B, q_len, st);
+// tp_size > 1 with a sampling / logprobs config: the ranks' [B][vocab] slices of bufs.logits side by side in d->gathered, [B][tp_size * vocab]
+// (bufs.logits keeps the rank's raw slice).  Attached context: the peer-read gather, one MI355_KC_COMM op per launch; external transport: its
+// all_gather of the contiguous block into the staging, then the reorder launch.
+int gather_logits(mi355_decoder* d, int B, hipStream_t st) {
+    const auto& c = d->cfg;
+    if (d->ar) {
+        const int n = mi355_allgather_logits_launches(d->ar, B, c.vocab);
+        if (n < 0) return n;
+        for (int part = 0; part < n; ++part)
+            RUN(MI355_KC_COMM, mi355_allgather_logits_part(d->ar, d->bufs.logits, c.vocab, d->gathered, B, c.vocab, part, st));
+        return MI355_OK;
+    }
+    RUN(MI355_KC_COMM, d->ext.all_gather(d->ext.ctx, d->bufs.logits, d->gather_stage, (size_t)B * c.vocab * 4, (mi355_stream_t)st) == 0
+                           ? MI355_OK : (mi355_set_error("decoder: the attached transport's all-gather failed"), MI355_ERR_HIP));
+    RUN(MI355_KC_OTHER, mi355_interleave_logits(d->gather_stage, d->gathered, c.tp_size, B, c.vocab, st));
+    return MI355_OK;
 }
-size_t sampling_penalty_bytes(const mi355_model_config_t& c) { return align256((size_t)c.max_batch * c.vocab * sizeof(int32_t)); }
+int step_tail(mi355_decoder* d, int B, int q_len, hipStream_t st) {
+    const auto& c = d->cfg;
+    if (c.tp_size > 1 && q_len == 1 && (d->sampling_on || d->logprobs_on)) {   // only reachable with the gathered buffer set (the setters refuse otherwise)
+        if (!d->gathered || (!d->ar && !d->has_ext)) { mi355_set_error("decoder: sampling / logprobs at tp_size %d without the gathered-logits buffer or a transport", c.tp_size); return MI355_ERR_ARG; }
+        const int VF = c.tp_size * c.vocab;
+        if (int e = gather_logits(d, B, st)) return e;
+        if (d->sampling_on) return sampled_tail(d, d->gathered, VF, B, st);
+        // greedy with log-probabilities: arg-max of the gathered row (lowest global index on ties: the id the cross-rank arg-max gives)
+        RUN(MI355_KC_OTHER, mi355_argmax_ex(d->gathered, B, VF, VF, d->bufs.token_ids, d->bufs.positions, d->argmax_ws, d->argmax_ws_bytes, st));
+        return logprob_tail(d, d->gathered, VF, B, 1, nullptr, st);
+    }
+    return d->sampling_on && q_len == 1 ? sampled_tail(d, d->bufs.logits, c.vocab, B, st) : greedy_tail(d, B, q_len, st);
+}
+// columns the sampled tail and the recorder see: the whole vocabulary under tensor parallelism (mi355_decoder_set_gathered_logits)
+int tail_cols(const mi355_model_config_t& c) { return c.tp_size > 1 ? c.tp_size * c.vocab : c.vocab; }
+size_t sampling_penalty_bytes(const mi355_model_config_t& c) { return align256((size_t)c.max_batch * tail_cols(c) * sizeof(int32_t)); }
+size_t gathered_rows_bytes(const mi355_model_config_t& c) { return align256((size_t)c.max_batch * c.tp_size * c.vocab * sizeof(float)); }
+// what a sampling / logprobs config needs at tp_size > 1, or 0: the gathered buffer, a transport, the rank's slice at rank * vocab of an evenly split vocabulary
+int tp_tail_problem(mi355_decoder* d, const char* who, const char* what) {
+    const auto& c = d->cfg;
+    if (!d->gathered) {
+        mi355_set_error("%s: tp_size %d: the lm_head is split over the vocabulary, %s tp_size 1", who, c.tp_size, what);
+        return MI355_ERR_UNSUPPORTED;
+    }
+    if (!d->ar && !d->has_ext) { mi355_set_error("%s: tp_size %d needs mi355_decoder_attach_allreduce / _attach_collective first", who, c.tp_size); return MI355_ERR_ARG; }
+    if (d->model.vocab_full != c.tp_size * c.vocab) {
+        mi355_set_error("%s: vocab_full %d != tp_size %d x vocab %d: a vocabulary that does not split evenly is not served", who, d->model.vocab_full, c.tp_size, c.vocab);
+        return MI355_ERR_UNSUPPORTED;
+    }
+    const int rank = d->ar ? mi355_allreduce_rank(d->ar) : d->ext.rank;
+    if (d->vocab_offset != rank * c.vocab) {
+        mi355_set_error("%s: vocab_offset %d of the attach call must be rank %d x vocab %d", who, d->vocab_offset, rank, c.vocab); return MI355_ERR_ARG;
+    }
+    return MI355_OK;
+}
 } // namespace
+
+extern "C" size_t mi355_decoder_gathered_logits_bytes(const mi355_model_config_t* cfg) {
+    if (!cfg || cfg->tp_size <= 1 || cfg->max_batch <= 0 || cfg->vocab <= 0) return 0;
+    return 2 * gathered_rows_bytes(*cfg);   // the gathered rows, then the staging of an external transport's all_gather ([tp_size][max_batch][vocab])
+}
+
+extern "C" int mi355_decoder_set_gathered_logits(mi355_decoder_t* d, float* buf, size_t bytes) {
+    if (!d) { mi355_set_error("decoder_set_gathered_logits: decoder is null"); return MI355_ERR_ARG; }
+    if (d->cfg.tp_size <= 1) { mi355_set_error("decoder_set_gathered_logits: tp_size 1 has nothing to gather"); return MI355_ERR_ARG; }
+    if (!buf) {
+        if (d->sampling_on || d->logprobs_on) {
+            mi355_set_error("decoder_set_gathered_logits: a sampling / logprobs config is active: clear it first"); return MI355_ERR_ARG;
+        }
+        drop_graphs(d); d->gathered = d->gather_stage = nullptr;
+        return MI355_OK;
+    }
+    if ((reinterpret_cast<uintptr_t>(buf) & 255) != 0) { mi355_set_error("decoder_set_gathered_logits: the buffer must be 256-byte aligned"); return MI355_ERR_ARG; }
+    if (d->cfg.vocab % 4 != 0) { mi355_set_error("decoder_set_gathered_logits: vocab %d per rank is not a multiple of 4", d->cfg.vocab); return MI355_ERR_UNSUPPORTED; }
+    const size_t need = mi355_decoder_gathered_logits_bytes(&d->cfg);
+    if (bytes < need) { mi355_set_error("decoder_set_gathered_logits: %zu bytes needed, %zu given", need, bytes); return MI355_ERR_WORKSPACE; }
+    drop_graphs(d);
+    d->gathered = buf; d->gather_stage = (float*)((char*)buf + gathered_rows_bytes(d->cfg));
+    return MI355_OK;
+}
 
 extern "C" size_t mi355_decoder_sampling_workspace_bytes(const mi355_model_config_t* cfg) {
     if (!cfg || cfg->max_batch <= 0 || cfg->vocab <= 0) return 0;
-    return sampling_penalty_bytes(*cfg) + align256(mi355_sample_logits_workspace_bytes(cfg->max_batch, cfg->vocab));
+    return sampling_penalty_bytes(*cfg) + align256(mi355_sample_logits_workspace_bytes(cfg->max_batch, tail_cols(*cfg)));
 }
 
 extern "C" int mi355_decoder_set_sampling(mi355_decoder_t* d, const mi355_sampling_t* s) {
     if (!d) { mi355_set_error("decoder_set_sampling: decoder is null"); return MI355_ERR_ARG; }
     if (!s) { drop_graphs(d); d->sampling_on = false; return MI355_OK; }
-    if (d->cfg.tp_size > 1) {
-        mi355_set_error("decoder_set_sampling: tp_size %d: the lm_head is split over the vocabulary, sampling needs tp_size 1", d->cfg.tp_size);
-        return MI355_ERR_UNSUPPORTED;
-    }
+    if (d->cfg.tp_size > 1) if (int e = tp_tail_problem(d, "decoder_set_sampling", "sampling needs")) return e;
     if (!s->seed) { mi355_set_error("decoder_set_sampling: seed [max_batch] is null"); return MI355_ERR_ARG; }
     const bool pen = s->repetition_penalty || s->presence_penalty || s->frequency_penalty;
     if ((pen || s->history || s->history_len) && (!s->history || !s->history_len || s->history_ld <= 0)) {
@@ -1066,16 +1150,13 @@ extern "C" int mi355_decoder_set_sampling(mi355_decoder_t* d, const mi355_sampli
 
 extern "C" size_t mi355_decoder_logprobs_workspace_bytes(const mi355_model_config_t* cfg, int32_t top_n) {
     if (!cfg || cfg->max_batch <= 0 || cfg->vocab <= 0) return 0;
-    return align256(mi355_logprobs_workspace_bytes(cfg->max_batch, cfg->vocab, top_n));
+    return align256(mi355_logprobs_workspace_bytes(cfg->max_batch, tail_cols(*cfg), top_n));
 }
 
 extern "C" int mi355_decoder_set_logprobs(mi355_decoder_t* d, const mi355_logprobs_t* lp) {
     if (!d) { mi355_set_error("decoder_set_logprobs: decoder is null"); return MI355_ERR_ARG; }
     if (!lp) { drop_graphs(d); d->logprobs_on = false; return MI355_OK; }
-    if (d->cfg.tp_size > 1) {
-        mi355_set_error("decoder_set_logprobs: tp_size %d: the lm_head is split over the vocabulary, log-probabilities need tp_size 1", d->cfg.tp_size);
-        return MI355_ERR_UNSUPPORTED;
-    }
+    if (d->cfg.tp_size > 1) if (int e = tp_tail_problem(d, "decoder_set_logprobs", "log-probabilities need")) return e;
     if (lp->top_n < 0 || lp->top_n > MI355_LOGPROBS_MAX_TOP) {
         mi355_set_error("decoder_set_logprobs: top_n %d outside [0, %d]", lp->top_n, MI355_LOGPROBS_MAX_TOP); return MI355_ERR_ARG;
     }

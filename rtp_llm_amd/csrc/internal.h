@@ -94,6 +94,13 @@ int mi355_logprobs_rows(const float* logits, int32_t rows, int32_t V, int32_t ld
                         int32_t top_n, float* token_logprobs, float* lse_out, int32_t* top_ids, float* top_logprobs, int32_t top_ld,
                         int32_t log_ld, int32_t* count, float* cum_log_probs, void* workspace, size_t workspace_bytes,
                         mi355_stream_t stream);
+/* allreduce.hip: mi355_allgather_logits launch by launch (the step driver runs and counts each as one MI355_KC_COMM op), the rank of a
+ * context, and the reorder behind an external transport's all_gather of the logits: [world][B][V] -> [B][world * V] */
+int mi355_allgather_logits_launches(mi355_allreduce_t* ar, int32_t B, int32_t V_local);
+int mi355_allgather_logits_part(mi355_allreduce_t* ar, const float* local, int32_t ld, float* out, int32_t B, int32_t V_local, int32_t part,
+                                mi355_stream_t stream);
+int mi355_allreduce_rank(const mi355_allreduce_t* ar);
+int mi355_interleave_logits(const float* staged, float* out, int32_t world, int32_t B, int32_t V, mi355_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

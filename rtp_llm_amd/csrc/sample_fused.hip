@@ -32,7 +32,7 @@ constexpr int kBins0 = 2048, kBins = 1024;
 constexpr float kMassScale = 1099511627776.0f;   // 2^40
 typedef unsigned long long u64;
 
-struct RowHist {                      // one level of one row; zero on entry (hipMemsetAsync node ahead of the launches)
+struct RowHist {                      // one level of one row; zero on entry (zero_fill launch ahead of the launches)
     uint32_t cnt_p[kBins0];
     uint32_t cnt_k[kBins0];
     u64      mass_p[kBins0];
@@ -519,6 +519,20 @@ __global__ __launch_bounds__(64) void sample_feedback_kernel(const int32_t* __re
     }
 }
 
+// Zero `bytes` (a multiple of 4, 4-byte aligned) with a launch of its own.  Not hipMemsetAsync: as a memset NODE of a captured step that also holds
+// the all-reduce launches of a tensor-parallel rank, it was observed to fill its range with a repeating 16-byte garbage pattern on every other
+// replay (the eager step was right every time) -- the histograms and the penalty counts then start a step non-zero.  A kernel node has no such state.
+__global__ __launch_bounds__(256) void zero_fill_kernel(uint32_t* __restrict__ p, size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) p[i] = 0u;
+}
+bool zero_fill(void* ptr, size_t bytes, hipStream_t st) {
+    const size_t n4 = bytes / 4;
+    if (n4 == 0) return true;
+    const size_t want = (n4 + 255) / 256;
+    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, (uint32_t*)ptr, n4);
+    return hipGetLastError() == hipSuccess;
+}
+
 struct WsLayout { size_t hist, state, segs, total; };
 WsLayout ws_layout(int rows) {
     WsLayout w;
@@ -555,9 +569,8 @@ extern "C" int mi355_sample_logits_ex(const float* logits, int32_t rows, int32_t
     }
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)workspace;
-    if (hipMemsetAsync(base + w.hist, 0, w.state - w.hist, st) != hipSuccess) {
-        (void)hipGetLastError();
-        mi355_set_error("sample_logits: hipMemsetAsync failed");
+    if (!zero_fill(base + w.hist, w.state - w.hist, st)) {
+        mi355_set_error("sample_logits: the zero-fill launch failed");
         return MI355_ERR_HIP;
     }
     SampleParams p{};
@@ -599,9 +612,8 @@ extern "C" int mi355_apply_penalties_history(float* logits, int32_t rows, int32_
     MI355_CHECK_ARG(history && history_len && history_ld > 0,
                     "apply_penalties_history: penalties need history [rows][history_ld] and history_len [rows]");
     MI355_CHECK_ARG(penalty_ws, "apply_penalties_history: penalty_ws [rows][V] int32 is null");
-    if (hipMemsetAsync(penalty_ws, 0, (size_t)rows * V * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        mi355_set_error("apply_penalties_history: hipMemsetAsync failed");
+    if (!zero_fill(penalty_ws, (size_t)rows * V * sizeof(int32_t), (hipStream_t)stream)) {
+        mi355_set_error("apply_penalties_history: the zero-fill launch failed");
         return MI355_ERR_HIP;
     }
     HistoryPenaltyParams p{logits, V, ld, repetition_penalty, presence_penalty, frequency_penalty, history, history_ld, history_len, penalty_ws};

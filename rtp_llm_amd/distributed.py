@@ -273,6 +273,18 @@ class CustomAllReduce:
         self._C.check(self.lib.mi355_allgather_hidden(self.handle, t.data_ptr(), out.data_ptr(), T, n, self._st()), "allgather_hidden")
         return out
 
+    def all_gather_logits(self, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 [B, V_local] logits slice per rank -> [B, V_local * world], slices side by side in rank order, bit for bit (the logits gather of a
+        vocab-split lm_head, PyWrappedModel.cc:915-936; mi355_allgather_logits).  V_local % 4 == 0.  A slice larger than the context's max_bytes
+        takes several launches (logits_gather_bytes sizes a context for one)."""
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1):
+            raise ValueError("all_gather_logits: fp32 [B, V_local] device tensor with unit column stride expected")
+        B, V = t.shape
+        if out is None:
+            out = torch.empty(B, V * self.world, dtype=torch.float32, device=t.device)
+        self._C.check(self.lib.mi355_allgather_logits(self.handle, t.data_ptr(), t.stride(0), out.data_ptr(), B, V, self._st()), "allgather_logits")
+        return out
+
     def argmax(self, logits_local: torch.Tensor, vocab_offset: int) -> torch.Tensor:
         B, V = logits_local.shape
         ids = torch.empty(B, dtype=torch.int32, device=logits_local.device)
@@ -353,6 +365,17 @@ class RcclTransport:
         if getattr(self, "handle", None):
             self.lib.mi355_rccl_close(self.handle)
             self.handle = None
+
+
+LOGITS_GATHER_UNIT = 4096     # bytes: the ownership unit of mi355_allgather_logits (csrc/allreduce.hip kUnitBytes)
+
+
+def logits_gather_bytes(B: int, V_local: int) -> int:
+    """The max_bytes of a CustomAllReduce context at which all_gather_logits of a [B, V_local] fp32 slice is ONE launch: the slice rounded up to
+    whole units (a smaller context still works, with ceil(slice / max_bytes) launches per call)."""
+    if B < 1 or V_local < 1:
+        raise ValueError("logits_gather_bytes: B and V_local must be positive")
+    return (B * V_local * 4 + LOGITS_GATHER_UNIT - 1) // LOGITS_GATHER_UNIT * LOGITS_GATHER_UNIT
 
 
 def set_custom_all_reduce(ar: Optional[CustomAllReduce]) -> None:

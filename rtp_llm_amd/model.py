@@ -517,6 +517,7 @@ class DecoderEngine:
         if cfg.qk_norm:   # Qwen3: before any step -- the QKV half of every layer becomes split-K + the normalising KV writer
             _C.check(self.lib.mi355_decoder_set_qk_norm(self.handle, qn_ptrs, kn_ptrs), "decoder_set_qk_norm")
         self.logprobs = None          # set_logprobs
+        self.full_logits = None       # enable_gathered_logits (tp > 1)
         self.kv_layout = _C.KV_LAYOUT_NATIVE
         if kv_layout != _C.KV_LAYOUT_NATIVE:
             self.set_kv_layout(kv_layout)
@@ -754,10 +755,41 @@ class DecoderEngine:
             raise _C.Mi355Error("generate_sampled: the KV writer dropped out-of-range tokens (corrupt block table?)")
         return torch.stack(out, 1).tolist()
 
+    # ---- tp > 1: the vocabulary-gathered logits the sampled tail and the log-probability recorder run on
+    def enable_gathered_logits(self):
+        """tp > 1: allocate the gathered-logits buffer (mi355_decoder_set_gathered_logits) and expose its rows as `self.full_logits`
+        [max_batch, tp_size * vocab] fp32.  Afterwards set_sampling / set_logprobs are accepted (every rank must pass identical parameters, seeds
+        and prompts: the ranks then draw identical tokens), and a decode step with either config active gathers the ranks' logits into
+        full_logits and runs its tail there.  Never enabled implicitly.  Captured graphs are dropped."""
+        nbytes = self.lib.mi355_decoder_gathered_logits_bytes(C.byref(self._structs[0]))
+        buf = torch.zeros(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        torch.cuda.synchronize()
+        _C.check(self.lib.mi355_decoder_set_gathered_logits(self.handle, buf.data_ptr(), nbytes), "decoder_set_gathered_logits")
+        self._gathered_buf = buf
+        n = self.max_batch * self.tp_size * self.cfg.vocab
+        self.full_logits = buf[: n * 4].view(torch.float32).view(self.max_batch, self.tp_size * self.cfg.vocab)
+        return self.full_logits
+
+    def disable_gathered_logits(self):
+        """The reverse; an error while a sampling / logprobs config is active (clear it first)."""
+        torch.cuda.synchronize()
+        _C.check(self.lib.mi355_decoder_set_gathered_logits(self.handle, None, 0), "decoder_set_gathered_logits")
+        self._gathered_buf = self.full_logits = None
+
+    def gather_logits(self, logits: torch.Tensor) -> torch.Tensor:
+        """tp > 1: this rank's [B, vocab] fp32 logits -> the full rows [B, tp_size * vocab] (the prefill logits of a sampled request): through the
+        attached all-reduce context when there is one, else torch.distributed over the TP group.  tp = 1: the tensor itself."""
+        if self.tp_size == 1:
+            return logits
+        ar = getattr(self, "_ar", None)
+        if ar is not None:
+            return ar.all_gather_logits(logits.contiguous())
+        return all_gather(logits.contiguous(), Group.TP).contiguous()
+
     # ---- sampled decoding inside the step
     def set_sampling(self, *, top_k=None, top_p=None, temperature=None, repetition_penalty=None, presence_penalty=None,
                      frequency_penalty=None, seeds=0, history_ld: Optional[int] = None):
-        """Give the step a sampling tail (mi355_decoder_set_sampling, tp = 1): step() / capture() / replay() then draw every token on
+        """Give the step a sampling tail (mi355_decoder_set_sampling; tp > 1: after enable_gathered_logits, identical arguments on every rank): step() / capture() / replay() then draw every token on
         the device -- penalties over the device-side history, temperature, top-k / top-p, Philox draw with the sequence's seed at the
         token's position -- and append it to the history.  Scalars or one value per sequence slot (max_batch); None leaves a filter /
         penalty out.  The engine allocates and owns the device arrays, exposed as `self.sampling` (dict of tensors: temperature,
@@ -801,7 +833,7 @@ class DecoderEngine:
 
     # ---- log-probabilities inside the step
     def set_logprobs(self, top_n: int = 0, log_ld: Optional[int] = None):
-        """Record the log-probability of every token the step chooses (mi355_decoder_set_logprobs, tp = 1), greedy or sampled, eager or
+        """Record the log-probability of every token the step chooses (mi355_decoder_set_logprobs; tp > 1: after enable_gathered_logits), greedy or sampled, eager or
         replayed: per sequence slot the token's value and the `top_n` alternatives (<= _C.LOGPROBS_MAX_TOP) of up to `log_ld` steps
         (default: the engine's capacity) and the running sum -- under the full-vocabulary softmax of the logits the token was chosen
         from (penalised and temperature-scaled under a sampling config).  The engine allocates and owns the device arrays, exposed as
@@ -879,7 +911,7 @@ class DecoderEngine:
         if s["history"].shape[1] < max(len(pr) for pr in prompts) + max_new_tokens:
             raise _C.Mi355Error("begin_sampled: the history of the sampling config is too short for this request")
         lens = torch.tensor([len(pr) for pr in prompts], dtype=torch.int32)
-        logits = self.prefill(prompts, block_table, chunk=prefill_chunk)
+        logits = self.gather_logits(self.prefill(prompts, block_table, chunk=prefill_chunk))   # tp > 1: the full rows, as at tp 1 from here on
         self.seed_history(prompts)
         self.set_inputs([0] * B, lens.tolist(), block_table)
         cut = lambda t: None if t is None else t[:B]
@@ -899,7 +931,7 @@ class DecoderEngine:
     def generate_sampled_graph(self, prompts: List[List[int]], block_table, max_new_tokens: int, *, top_k=None, top_p=None, temperature=None,
                                repetition_penalty=None, presence_penalty=None, frequency_penalty=None, seeds=0,
                                prefill_chunk: int = 512, reuse_sampling: bool = False, top_logprobs: Optional[int] = None):
-        """Sampled generation with every decode step inside the captured graph (tp = 1): prefill, the history seeded with the prompts,
+        """Sampled generation with every decode step inside the captured graph (tp > 1: after enable_gathered_logits, the same call on every rank): prefill, the history seeded with the prompts,
         the first token drawn from the prefill logits by the same ops under the same position convention (the token at position p of
         a sequence uses the Philox number of (its seed, p)), then max_new_tokens - 1 replayed steps and ONE read of the history.
         reuse_sampling: keep the config and the graph of the previous call (the host may have rewritten `self.sampling` in place).
@@ -969,6 +1001,8 @@ class DecoderEngine:
 
     # ---- tp > 1: the step cut at the all-reduce points (causal_attention.py:91-92, dense_mlp.py:104-105)
     def step_tp(self, B: int, sample: bool = True):
+        """The Python-segmented TP step (host all-reduce between the segments).  Greedy only: the sampling / logprobs configs of the C++ step
+        (enable_gathered_logits) do not apply here."""
         if getattr(self, "_transport", None) is not None:
             raise _C.Mi355Error("step_tp: a transport is attached, the C++ step already all-reduces: use step()")
         st, h, lib = self._st(), self.handle, self.lib
