@@ -46,9 +46,12 @@ enum {
 
 /* weight element kinds */
 enum { MI355_W4 = 4, MI355_W8 = 8, MI355_W16 = 16 };
-/* what the stored codes of a weight are (mi355_weight_t.wkind): integers with {zneg, scale} meta, or OCP FP8 e4m3 bit patterns
- * with an fp32 scale per (128-row group, column) -- see "FP8 weights" at mi355_weight_t */
-enum { MI355_WKIND_INT = 0, MI355_WKIND_FP8_E4M3 = 1 };
+/* what the stored codes of a weight are (mi355_weight_t.wkind): integers with {zneg, scale} meta, OCP FP8 e4m3 bit patterns
+ * with an fp32 scale per (128-row group, column) -- see "FP8 weights" at mi355_weight_t -- or OCP MXFP4: e2m1 codes with one
+ * e8m0 scale byte per (32-row group, column) -- see "MXFP4 weights" there.  MI355_WKIND_MXFP4 was added without raising
+ * MI355_ABI_VERSION: the struct, every existing value and every existing entry point keep their meaning, a library that
+ * predates it answers the new value with MI355_ERR_ARG ("wkind"). */
+enum { MI355_WKIND_INT = 0, MI355_WKIND_FP8_E4M3 = 1, MI355_WKIND_MXFP4 = 2 };
 /* KV-cache element kinds (reference: KvCacheDataType, cpp/model_utils/AttentionConfig.h:9-12;
  * value 1 is the INT8 slot the reference removed, kept here) */
 enum { MI355_KV_FP16 = 0, MI355_KV_INT8 = 1, MI355_KV_BF16 = 2 };
@@ -106,6 +109,29 @@ const char* mi355_last_error(void);
  *   Served by the staged decode kernels (mi355_linear_forward / _partial / _direct, M <= 8 fp16 also by the persistent kernel); every
  *   fused / image launch and its *_ok / *_plan predicate refuses the kind (MI355_ERR_UNSUPPORTED / 0), the step driver then
  *   composes the staged chain.
+ *
+ * MXFP4 weights (wkind = MI355_WKIND_MXFP4; OCP microscaling FP4, the weight form of the Quark "fp4" / "e8m0" per-group-32
+ * checkpoints).  Requires wbits == MI355_W4 and group_size == 32, anything else is MI355_ERR_ARG.  Weight-only: activations stay
+ * 16-bit, which is a different (more accurate) computation than the W4A4 scheme such checkpoints declare.
+ *   `qweight` is the W4 tile image above with the same tile, wave-load and lane addressing (tile (nt, c), 1 wave-load, lane
+ *   l = i + 16q, dword s of the lane's 16 bytes = MFMA k-step s, rows k = 128c + 32s + 8q + e), but the nibble order is the
+ *   natural one: code e sits at bit 4e of dword s (byte j holds element 2j in its low nibble, 2j + 1 in its high nibble), the
+ *   order v_cvt_scalef32_pk_*_fp4 reads.  A code is the e2m1 bit pattern (sign, 2 exponent bits, 1 mantissa bit): values
+ *   +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}.  Padding rows / columns hold code 0.
+ *   `meta[c * N_pad + n]` is one dword per (128-row chunk c, column n) -- the slot and indexing of a g128 meta plane, 4.25 bits
+ *   per weight in total.  Byte s of it is the e8m0 scale byte of rows 128c + 32s .. + 31 of column n, value 2^(byte - 127); the
+ *   kernel forms the fp32 scale as byte << 23.  Padding holds byte 127.
+ *       W[k][n] = e2m1(code) * 2^(byte[k / 32][n] - 127).
+ *   Numerics contract: the MFMA operand is fp16(2^E * e2m1) (bf16 for bf16 activations), produced by the conversion itself.
+ *   It is exact, and a normal number, exactly when E = byte - 127 is in [-13, 13] for every group with a nonzero code (smallest
+ *   product 0.5 * 2^-13 = 2^-14, largest 6 * 2^13 = 49152); the packer (quant.pack_mxfp4) enforces that range for both
+ *   activation dtypes: E > 13 or byte 255 (NaN) is refused, a group with E < -13 is flushed to zero codes with byte 127 (every
+ *   weight in it is below 6 * 2^-14), an all-zero group gets byte 127.  Then y = x @ W with exact products, fp32 MFMA
+ *   accumulation over all of K and one rounding at the output: no zero point, no group sums of x, no accumulator-side scale.
+ *   Served by the staged decode kernels (mi355_linear_forward / _partial / _direct at every M, M >= 128 as 64-row slabs; M <= 8
+ *   fp16 also by the persistent kernel); every fused / image launch and its *_ok / *_plan predicate refuses the kind
+ *   (MI355_ERR_UNSUPPORTED / 0), the step driver then composes the staged chain.  Not served: FP4 / FP8 activations and the scaled
+ *   MFMA, NVFP4, an MXFP4 lm_head.
  * ---------------------------------------------------------------------- */
 typedef struct {
     const void* qweight; /* dev */
@@ -117,7 +143,7 @@ typedef struct {
     int32_t     N_pad;   /* multiple of 16 */
     int32_t     group_size; /* 32, 64, 128, or 0 = per-channel */
     int32_t     act_dtype;  /* MI355_ACT_F16 / MI355_ACT_BF16: dtype of x, bias, y (and of the elements of a W16 weight) */
-    int32_t     wkind;      /* MI355_WKIND_*: 0 = integer codes, so a zero-initialised struct keeps its meaning (sizeof stays 48) */
+    int32_t     wkind;      /* MI355_WKIND_* (0 / 1 / 2): 0 = integer codes, so a zero-initialised struct keeps its meaning (sizeof stays 48) */
 } mi355_weight_t;
 
 /* epilogue flags for mi355_linear_forward */

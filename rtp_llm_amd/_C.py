@@ -22,7 +22,7 @@ EPI_NONE, EPI_SILU_MUL, EPI_OUT_F32, EPI_OUT_IMAGE = 0, 1, 2, 4
 PF_QKV, PF_O, PF_GATE_UP, PF_QKV_LATE, PF_O_LATE, PF_TP_COMM, PF_TP_INLAUNCH, PF_QKV_IN_FOLD = 1, 2, 4, 16, 32, 64, 128, 256   # mi355_decoder_set_weight_prefetch mask bits
 HINT_STAGED, HINT_NO_PERSISTENT = 0x100, 0x200
 ABI_VERSION = 5
-WKIND_INT, WKIND_FP8_E4M3 = 0, 1   # mi355_weight_t.wkind
+WKIND_INT, WKIND_FP8_E4M3, WKIND_MXFP4 = 0, 1, 2   # mi355_weight_t.wkind
 LOGPROBS_MAX_TOP = 32
 KC_NAMES = ["gemm_quant", "gemm_lmhead", "attn", "rope_kv", "norm", "other", "comm"]
 

@@ -899,7 +899,7 @@ size_t linear_ws_bound(const mi355_model_config_t& c) {
         for (int wbits : {4, 8, 16}) {
             mi355_weight_t w;
             w.qweight = &need; w.meta = &need; w.wbits = wbits; w.wkind = MI355_WKIND_INT; w.K = sh[0]; w.N = sh[1]; w.act_dtype = c.act_dtype;   // bf16 plans other block shapes (and splits) above 32 rows
-            w.K_pad = (sh[0] + 127) & ~127; w.N_pad = (sh[1] + 15) & ~15; w.group_size = wbits == 4 ? 128 : 0;
+            w.K_pad = (sh[0] + 127) & ~127; w.N_pad = (sh[1] + 15) & ~15; w.group_size = wbits == 4 ? 128 : 0;   // the split plan reads wbits, not wkind / group_size: FP8 and MXFP4 are covered by 8 and 4
             need = std::max(need, mi355_linear_workspace_bytes(64, &w));
         }
     return need;

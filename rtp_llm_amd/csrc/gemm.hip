@@ -73,15 +73,20 @@ namespace {
 // (group, column).  The byte is widened to the exact fp16 / bf16 image of its value (widen_fp8*, 4 VALU per 8 weights as widen_w8), a group's
 // products are summed in fp32 and the fp32 scale multiplies that sum on the accumulator side at EVERY row-block count: acc += scale * ag.
 // There is no zero point, so no sums of x (xsum) either.
-template <int WBITS, int MB, int NBW, int GS, int D, int NWN, int KG, bool BF = false, bool F8 = false>
+// MX: MXFP4 (wkind = MI355_WKIND_MXFP4; WBITS = 4, GS = 4): e2m1 codes in the W4 tile image and one meta dword per (chunk, column) holding
+// the four e8m0 scale bytes of the chunk's 32-row groups.  A group is one MFMA k-step, so the scale is applied on the OPERAND side by the
+// conversion itself (widen_mxfp4*: the operand is the exact 2^E * e2m1) and the products go straight into acc, as for 16-bit weights: no
+// accumulator-side work, no xsum, at every row-block count.
+template <int WBITS, int MB, int NBW, int GS, int D, int NWN, int KG, bool BF = false, bool F8 = false, bool MX = false>
 __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams p) {
     static_assert(!F8 || (WBITS == 8 && GS == 4), "FP8 weights: 8-bit codes, 128-row groups");
+    static_assert(!MX || (WBITS == 4 && GS == 4 && !F8), "MXFP4 weights: 4-bit codes, one meta dword per 128-row chunk");
     constexpr int LPC    = WBITS / 4;              // wave-loads per (tile, chunk)
     constexpr int NSUB   = (GS > 0) ? 4 / GS : 1;  // quantisation groups per chunk (per-channel: 1 pseudo group)
     constexpr int SPG    = 4 / NSUB;               // MFMA k-steps per group
     constexpr bool QUANT = WBITS != 16;
     constexpr bool GROUPED = GS > 0;               // per-group scale (else one scale per column, applied at the end)
-    constexpr bool CSIDE = QUANT && (MB <= 2 || BF || F8); // zero/scale on the accumulator side (cheap for few row blocks);
+    constexpr bool CSIDE = QUANT && !MX && (MB <= 2 || BF || F8); // zero/scale on the accumulator side (cheap for few row blocks);
                                                    // MB >= 3: classic operand-side dequant, cost independent of MB
     constexpr int GT     = 64 * NWN;               // threads per k-group
     constexpr int XSLOTS = 256 * MB;               // 16-byte slots per x chunk tile
@@ -268,6 +273,9 @@ __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams
                     u32x4 a;
                     if (WBITS == 16) {
                         a = wr[d][nb][s % LPC];
+                    } else if (MX) {   // byte s of the lane's meta dword (column 16nt + jj, the A operand's column) scales k-step s
+                        const float sc = mxfp4_scale(mr[d][nb][0], s);
+                        a = BF ? widen_mxfp4_bf16(wr[d][nb][0][s], sc) : widen_mxfp4(wr[d][nb][0][s], sc);
                     } else if (CSIDE) {
                         if (WBITS == 4) {
                             if (BF) a = widen_w4_bf16(wr[d][nb][0][s]);
@@ -387,7 +395,7 @@ __global__ __launch_bounds__(64 * NWN * KG) void gemm_wq_kernel(const GemmParams
 
     auto slot = [&](int d, int ci) {
         load_x((d + XR - 1) % XR, ci + XR - 1);  // OOB -> zeros past the end
-        if (QUANT && !CSIDE) compute_os(d, d & 1);
+        if (QUANT && !CSIDE && !MX) compute_os(d, d & 1);
         else compute(d, d & 1);                  // D is even, so ci & 1 == d & 1
         load_w(d, ci + D);
         store_x((d + 1) % XR, (d + 1) & 1);       // chunk ci+1, issued XR-2 iterations ago
@@ -559,42 +567,42 @@ constexpr int kCfgBN[13] = {64, 128, 128, 256, 256, 64, 256, 256, 128, 128, 256,
 
 // Ring depths per shape: D1 for the M<=16 shapes, D2 for BN=128 (M<=32), DW for the 16-wave BN=256 shapes.
 // Bytes in flight per CU = waves * NBW * D KiB; ~85 KiB per CU are needed to cover HBM latency at 6 TB/s.
-template <int WBITS, int GS, int D1, int D2, int DW, bool F8 = false>
+template <int WBITS, int GS, int D1, int D2, int DW, bool F8 = false, bool MX = false>
 int launch_gemm_t(const GemmParams& p, int cfg, hipStream_t st) {
     dim3 grid(cdiv(p.NT * 16, kCfgBN[cfg]), p.nsplit);
     if (cfg == 3) cfg = 4;   // (the three-row-block shapes 3 / 7 are gone: 33..48 rows run on the four-row-block ones)
     if (cfg == 7) cfg = 6;
     switch (cfg) {
-        case 0: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 2, false, F8>), grid, dim3(512), 0, st, p); break;
-        case 1: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 2, GS, D1, 4, 2, false, F8>), grid, dim3(512), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 2, 1, GS, D2, 8, 1, false, F8>), grid, dim3(512), 0, st, p); break;
-        case 4: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 8, 1, false, F8>), grid, dim3(512), 0, st, p); break;
-        case 5: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 1, false, F8>), grid, dim3(256), 0, st, p); break;
-        case 6: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, 2, 16, 1, false, F8>), grid, dim3(1024), 0, st, p); break;
-        case 8: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 8, 1, false, F8>), grid, dim3(512), 0, st, p); break;
-        case 9: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 4, 1, false, F8>), grid, dim3(256), 0, st, p); break;
-        case 10: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 4, GS, 2, 4, 1, false, F8>), grid, dim3(256), 0, st, p); break;
-        case 11: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 10, 1, false, F8>), grid, dim3(640), 0, st, p); break;
-        default: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 4, 1, false, F8>), grid, dim3(256), 0, st, p); break;
+        case 0: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 2, false, F8, MX>), grid, dim3(512), 0, st, p); break;
+        case 1: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 2, GS, D1, 4, 2, false, F8, MX>), grid, dim3(512), 0, st, p); break;
+        case 2: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 2, 1, GS, D2, 8, 1, false, F8, MX>), grid, dim3(512), 0, st, p); break;
+        case 4: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 8, 1, false, F8, MX>), grid, dim3(512), 0, st, p); break;
+        case 5: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 1, false, F8, MX>), grid, dim3(256), 0, st, p); break;
+        case 6: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, 2, 16, 1, false, F8, MX>), grid, dim3(1024), 0, st, p); break;
+        case 8: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 8, 1, false, F8, MX>), grid, dim3(512), 0, st, p); break;
+        case 9: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 4, 1, false, F8, MX>), grid, dim3(256), 0, st, p); break;
+        case 10: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 4, GS, 2, 4, 1, false, F8, MX>), grid, dim3(256), 0, st, p); break;
+        case 11: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 10, 1, false, F8, MX>), grid, dim3(640), 0, st, p); break;
+        default: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 4, 1, false, F8, MX>), grid, dim3(256), 0, st, p); break;
     }
     MI355_CHECK_LAUNCH("gemm_wq_kernel");
     return MI355_OK;
 }
 
 // bf16 activations: the three shapes the planner picks by row-block count (+ the narrow-N shape 8), nothing else instantiated
-template <int WBITS, int GS, int D1, int D2, int DW, bool F8 = false>
+template <int WBITS, int GS, int D1, int D2, int DW, bool F8 = false, bool MX = false>
 int launch_gemm_bf16_t(const GemmParams& p, int cfg, hipStream_t st) {
     dim3 grid(cdiv(p.NT * 16, kCfgBN[cfg]), p.nsplit);
     switch (cfg) {
-        case 1: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 2, GS, D1, 4, 2, true, F8>), grid, dim3(512), 0, st, p); break;
-        case 5: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 1, true, F8>), grid, dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 2, 1, GS, D2, 8, 1, true, F8>), grid, dim3(512), 0, st, p); break;
-        case 8: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 8, 1, true, F8>), grid, dim3(512), 0, st, p); break;
-        case 6: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, 2, 16, 1, true, F8>), grid, dim3(1024), 0, st, p); break;
+        case 1: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 2, GS, D1, 4, 2, true, F8, MX>), grid, dim3(512), 0, st, p); break;
+        case 5: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 1, 1, GS, D1, 4, 1, true, F8, MX>), grid, dim3(256), 0, st, p); break;
+        case 2: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 2, 1, GS, D2, 8, 1, true, F8, MX>), grid, dim3(512), 0, st, p); break;
+        case 8: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 8, 1, true, F8, MX>), grid, dim3(512), 0, st, p); break;
+        case 6: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, 2, 16, 1, true, F8, MX>), grid, dim3(1024), 0, st, p); break;
 #ifdef MI355_TUNING   // other shapes tried for the four-row-block bf16 case (tools/gemm_bench.py --bf16 1 --nbw N): all behind 6 / 8
-        case 9: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 4, 1, true, F8>), grid, dim3(256), 0, st, p); break;
-        case 10: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 4, GS, 2, 4, 1, true, F8>), grid, dim3(256), 0, st, p); break;
-        case 12: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 4, 1, true, F8>), grid, dim3(256), 0, st, p); break;
+        case 9: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 2, GS, DW, 4, 1, true, F8, MX>), grid, dim3(256), 0, st, p); break;
+        case 10: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 4, GS, 2, 4, 1, true, F8, MX>), grid, dim3(256), 0, st, p); break;
+        case 12: hipLaunchKernelGGL((gemm_wq_kernel<WBITS, 4, 1, GS, DW, 4, 1, true, F8, MX>), grid, dim3(256), 0, st, p); break;
 #endif
         default: mi355_set_error("gemm (bf16): block shape %d not built", cfg); return MI355_ERR_UNSUPPORTED;
     }
@@ -602,8 +610,12 @@ int launch_gemm_bf16_t(const GemmParams& p, int cfg, hipStream_t st) {
     return MI355_OK;
 }
 
-// wbits: the format code of mi355_wfmt (internal.h): 4 / 8 / 16, or MI355_WFMT_FP8
+// wbits: the format code of mi355_wfmt (internal.h): 4 / 8 / 16, MI355_WFMT_FP8 or MI355_WFMT_MXFP4
 int launch_gemm(const GemmParams& p, int wbits, int group_size, int cfg, hipStream_t st) {
+    if (wbits == MI355_WFMT_MXFP4) {   // ring depths of W4 g128: same bytes per chunk
+        if (group_size != 32) { mi355_set_error("gemm: MXFP4 weights need group_size 32 (got %d)", group_size); return MI355_ERR_UNSUPPORTED; }
+        return p.bf16 ? launch_gemm_bf16_t<4, 4, 4, 4, 4, false, true>(p, cfg, st) : launch_gemm_t<4, 4, 4, 4, 4, false, true>(p, cfg, st);
+    }
     if (wbits == MI355_WFMT_FP8) {
         if (group_size != 128) { mi355_set_error("gemm: FP8 weights need group_size 128 (got %d)", group_size); return MI355_ERR_UNSUPPORTED; }
         return p.bf16 ? launch_gemm_bf16_t<8, 4, 4, 2, 2, true>(p, cfg, st) : launch_gemm_t<8, 4, 4, 2, 2, true>(p, cfg, st);
@@ -645,9 +657,11 @@ int check_weight(const mi355_weight_t* w) {
     MI355_CHECK_ARG(w->wbits == 16 || w->meta, "linear: quantized weight needs meta");
     MI355_CHECK_ARG((uint64_t)w->K_pad * w->N_pad * w->wbits / 8 < 0xFFFFFFF0ull, "linear: weight image >= 4 GiB");
     MI355_CHECK_ARG(w->act_dtype == MI355_ACT_F16 || w->act_dtype == MI355_ACT_BF16, "linear: act_dtype=%d", w->act_dtype);
-    MI355_CHECK_ARG(w->wkind == MI355_WKIND_INT || w->wkind == MI355_WKIND_FP8_E4M3, "linear: wkind=%d", w->wkind);
+    MI355_CHECK_ARG(w->wkind == MI355_WKIND_INT || w->wkind == MI355_WKIND_FP8_E4M3 || w->wkind == MI355_WKIND_MXFP4, "linear: wkind=%d", w->wkind);
     MI355_CHECK_ARG(w->wkind != MI355_WKIND_FP8_E4M3 || (w->wbits == MI355_W8 && w->group_size == 128),
                     "linear: FP8 e4m3 weights are wbits 8 with 128-row groups (got wbits=%d group_size=%d)", w->wbits, w->group_size);
+    MI355_CHECK_ARG(w->wkind != MI355_WKIND_MXFP4 || (w->wbits == MI355_W4 && w->group_size == 32),
+                    "linear: wkind MXFP4 weights are wbits 4 with 32-row groups (got wbits=%d group_size=%d)", w->wbits, w->group_size);
     return MI355_OK;
 }
 
@@ -655,7 +669,8 @@ void fill_params(GemmParams& p, const void* x, int M, const mi355_weight_t* w) {
     p.x = (const f16*)x; p.qw = w->qweight; p.meta = (const uint32_t*)w->meta;
     p.M = M; p.K = w->K; p.N = w->N; p.N_pad = w->N_pad; p.NT = w->N_pad / 16; p.KC = w->K_pad / 128;
     p.qw_bytes = (uint32_t)((uint64_t)w->K_pad * w->N_pad * w->wbits / 8);
-    const int ngroups = (w->wbits == 16) ? 0 : (w->group_size > 0 ? w->K_pad / w->group_size : 1);
+    const int ngroups = (w->wbits == 16) ? 0 : w->wkind == MI355_WKIND_MXFP4 ? w->K_pad / 128   // one dword of four e8m0 bytes per chunk
+                      : (w->group_size > 0 ? w->K_pad / w->group_size : 1);
     p.meta_bytes = (uint32_t)((uint64_t)ngroups * w->N_pad * 4);
     p.x_bytes = (uint32_t)((uint64_t)M * w->K * 2);
     p.bias = nullptr; p.y = nullptr; p.partials = nullptr; p.ldy = 0;
@@ -889,7 +904,7 @@ extern "C" int mi355_linear_direct(const void* x, int32_t M, const mi355_weight_
 // ------------------------------------------------------------------ full-K kernels with fused consumers (gemm_fullk.hip)
 extern "C" int mi355_fullk_weight_ok(const mi355_weight_t* w) {
     if (w && w->act_dtype != MI355_ACT_F16) return 0;   // the full-K fused launches exist for fp16 activations only
-    if (w && w->wkind != MI355_WKIND_INT) return 0;     // integer codes only: an FP8 weight would be decoded as INT8
+    if (w && w->wkind != MI355_WKIND_INT) return 0;     // integer codes only: an FP8 weight would be decoded as INT8, an MXFP4 one as W4 g32
     const bool fmt = w && w->qweight && ((w->wbits == 4 && w->meta && (w->group_size == 128 || w->group_size == 64 || w->group_size == 32)) || w->wbits == 16);
     return fmt && w->K % 128 == 0 && w->K_pad == w->K && w->K_pad / 128 >= 4 && w->N % 16 == 0;
 }
@@ -897,7 +912,7 @@ extern "C" int mi355_fullk_weight_ok(const mi355_weight_t* w) {
 // the launches on activation images (gemm_fullk64 / gemm_splitk64 / gemm_wide image entries): W4 group-wise weights in the native
 // image; the activation dtype of the surrounding tensors is free (the image itself is fp16, see common.h)
 static bool img_weight_ok(const mi355_weight_t* w) {
-    if (w && w->wkind != MI355_WKIND_INT) return false;   // no FP8 instances of the image launches
+    if (w && w->wkind != MI355_WKIND_INT) return false;   // no FP8 / MXFP4 instances of the image launches
     const bool fmt = w && w->qweight && w->meta && ((w->wbits == 4 && (w->group_size == 128 || w->group_size == 64 || w->group_size == 32)) ||
                                                     (w->wbits == 8 && w->group_size == 0));   // round 5: per-channel W8 (load-time INT8 autoquant)
     return fmt && w->K % 128 == 0 && w->K_pad == w->K && w->K_pad / 128 >= 4 && w->N % 16 == 0;

@@ -267,6 +267,31 @@ __device__ __forceinline__ u32x4 widen_fp8_bf16(uint32_t lo, uint32_t hi) {
     return r;
 }
 
+// MXFP4 (OCP microscaling: e2m1 codes, one e8m0 scale per 32 weights) -> fp16 / bf16 of  2^E * e2m1.  One dword holds the 8 codes of
+// one MFMA k-step, code e at bit 4e; v_cvt_scalef32_pk_*_fp4 converts one byte (sel 0..3: two codes, low nibble first) and multiplies
+// by the fp32 scale operand, so the e8m0 scale is applied on the operand side for free: 4 VALU per 8 weights.  With E in [-13, 13]
+// (what the packer admits) every product is a normal fp16 / bf16 number and exact.
+__device__ __forceinline__ u32x4 widen_mxfp4(uint32_t w, float scale) {
+    u32x4 r;
+    r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 0));
+    r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 1));
+    r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 2));
+    r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 3));
+    return r;
+}
+__device__ __forceinline__ u32x4 widen_mxfp4_bf16(uint32_t w, float scale) {
+    u32x4 r;
+    r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
+    r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
+    r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
+    r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
+    return r;
+}
+// the fp32 scale 2^(byte - 127) of k-step s from the meta dword of (chunk, column): the e8m0 byte is the fp32 exponent field
+__device__ __forceinline__ float mxfp4_scale(uint32_t meta, int s) {
+    return __builtin_bit_cast(float, ((meta >> (8 * s)) & 0xFFu) << 23);
+}
+
 // Operand-side dequant (M > 32): scale * (u - z) in fp16 — exact subtract of the biased code, one rounding.
 // Even code pairs come out as 1024+u, odd pairs as 64+u (see widen_w4), so the subtract uses two exact
 // constants -(1024+z) and -(64+z).  1 shift + 4 v_and_or + 4 v_pk_add + 4 v_pk_mul = 13 VALU per 8 weights.

@@ -28,9 +28,12 @@ struct SmallMParams {
 
 // F8: FP8 e4m3 bytes with one fp32 scale per (128-row group, column) (mi355_weight_t.wkind; gemm.hip): the exact fp16 image of the byte into
 // the MFMA, acc += scale * (fp32 sum of the group); no zero point, so no indicator MFMAs.
-template <int WBITS, int GS, int D, int NW, bool F8 = false>
+// MX: MXFP4 (e2m1 codes, one meta dword of four e8m0 bytes per (chunk, column); gemm.hip): the scale goes into the conversion, the operand is the
+// exact 2^E * e2m1 and the products accumulate straight into acc; the lane reads the meta dword of its A-operand column (16 tile + jj).
+template <int WBITS, int GS, int D, int NW, bool F8 = false, bool MX = false>
 __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams sp) {
     static_assert(!F8 || (WBITS == 8 && GS == 4), "FP8 weights: 8-bit codes, 128-row groups");
+    static_assert(!MX || (WBITS == 4 && GS == 4 && !F8), "MXFP4 weights: 4-bit codes, one meta dword per 128-row chunk");
     const GemmParams& p = sp.g;
     constexpr int LPC  = WBITS / 4;
     constexpr int NSUB = (GS > 0) ? 4 / GS : 1;
@@ -77,7 +80,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams
 
     u32x4    wr[D][LPC];
     u32x4    mr[D][NSUB];                         // meta {zneg, scale} of this lane's 4 output columns (C layout)
-    const uint32_t lane16 = lane * 16u, q16 = q * 16u;
+    uint32_t mx[D];                               // MXFP4: the four e8m0 bytes of this lane's A-operand column
+    const uint32_t lane16 = lane * 16u, q16 = q * 16u, jj4 = jj * 4u;
     const W4Consts w4c = w4_consts();
 
     // Cursors advance by constant strides (a handful of SALU per unit; an earlier version recomputed
@@ -99,7 +103,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams
         const uint32_t woff = (pf_w & okm) | (OOBS & ~okm);
 #pragma unroll
         for (int lp = 0; lp < LPC; ++lp) wr[d][lp] = bload128<2 /*nt*/>(rw, lane16, woff + ((lp * 1024u) & okm));
-        if (GROUPED) {
+        if (MX) {
+            mx[d] = __builtin_amdgcn_raw_buffer_load_b32(rm, jj4, (pf_m & okm) | (OOBS & ~okm), 0);
+        } else if (GROUPED) {
 #pragma unroll
             for (int gi = 0; gi < NSUB; ++gi)
                 mr[d][gi] = bload128<0>(rm, q16, ((pf_m + gi * npad4) & okm) | (OOBS & ~okm));
@@ -142,6 +148,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams
             for (int ss = 0; ss < SPG; ++ss) {
                 const int s = gi * SPG + ss;
                 const f16x8 b = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(smem + xbase + s * 64));
+                if (MX) {
+                    acc = mfma16x16x32(__builtin_bit_cast(f16x8, widen_mxfp4(wr[d][0][s], mxfp4_scale(mx[d], s))), b, acc);
+                    continue;
+                }
                 if (!F8) x0a = mfma16x16x32(ind0, b, x0a);
                 if (WBITS == 4) x1a = mfma16x16x32(ind1, b, x1a);
                 f16x8 a;
@@ -157,7 +167,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams
                 ag = mfma16x16x32(a, b, ag);
             }
             const float XS = x0a[0] + x1a[0], XB = 960.f * x1a[0];
-            if (F8) {
+            if (MX) {
+                // accumulated straight into acc
+            } else if (F8) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(__builtin_bit_cast(float, mr[d][gi][r]), ag[r], acc[r]);
             } else if (GROUPED) {
@@ -209,10 +221,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_smallm_kernel(const SmallMParams
     }
 }
 
-template <int WBITS, int GS, int D = 4, bool F8 = false>
+template <int WBITS, int GS, int D = 4, bool F8 = false, bool MX = false>
 int launch_t(const SmallMParams& sp, size_t lds, hipStream_t st) {
     constexpr int NW = 16;
-    auto k = gemm_smallm_kernel<WBITS, GS, D, NW, F8>;
+    auto k = gemm_smallm_kernel<WBITS, GS, D, NW, F8, MX>;
     if (int e = raise_dynamic_lds((const void*)k, "gemm_smallm")) return e; // allow > 64 KiB of dynamic LDS
     hipLaunchKernelGGL(k, dim3(sp.GT, sp.g.nsplit), dim3(64 * NW), lds, st, sp);
     MI355_CHECK_LAUNCH("gemm_smallm_kernel");
@@ -227,8 +239,10 @@ extern "C" int mi355_gemm_smallm(const void* gp, int wbits, int group_size, int 
                                  mi355_stream_t stream) {
     GemmParams g = *reinterpret_cast<const GemmParams*>(gp);
     const bool fp8 = wbits == MI355_WFMT_FP8;         // format code of mi355_wfmt (internal.h)
+    const bool mx = wbits == MI355_WFMT_MXFP4;
     if (fp8 && (group_size != 128 || g.bf16)) return MI355_ERR_UNSUPPORTED;
-    if (g.M > 8 || (wbits != 4 && wbits != 8 && !fp8)) return MI355_ERR_UNSUPPORTED;
+    if (mx && (group_size != 32 || g.bf16)) return MI355_ERR_UNSUPPORTED;
+    if (g.M > 8 || (wbits != 4 && wbits != 8 && !fp8 && !mx)) return MI355_ERR_UNSUPPORTED;
     if (wbits == 4 && !(group_size == 128 || group_size == 64 || group_size == 32)) return MI355_ERR_UNSUPPORTED;
     if (wbits == 8 && !(group_size == 0 || group_size == 128)) return MI355_ERR_UNSUPPORTED;
     constexpr int NW = 16, CUS = 256;
@@ -260,7 +274,8 @@ extern "C" int mi355_gemm_smallm(const void* gp, int wbits, int group_size, int 
 #ifdef MI355_TUNING
     if (wbits == 4 && group_size == 128 && TUNE(3) == 1) return (rc = launch_t<4, 4, 8>(sp, lds, st)) < 0 ? rc : g.nsplit;
 #endif
-    if (fp8)        rc = launch_t<8, 4, 4, true>(sp, lds, st);
+    if (mx)         rc = launch_t<4, 4, 4, false, true>(sp, lds, st);
+    else if (fp8)   rc = launch_t<8, 4, 4, true>(sp, lds, st);
     else if (wbits == 4) rc = group_size == 128 ? launch_t<4, 4>(sp, lds, st) : group_size == 64 ? launch_t<4, 2>(sp, lds, st) : launch_t<4, 1>(sp, lds, st);
     else            rc = group_size == 0 ? launch_t<8, 0>(sp, lds, st) : launch_t<8, 4>(sp, lds, st);
     return rc < 0 ? rc : g.nsplit;

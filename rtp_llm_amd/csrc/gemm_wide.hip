@@ -398,7 +398,7 @@ static int gemm_wide_launch(const void* gp, int wbits, int group_size, int want_
 // does the direct (one launch, no slabs) form take this linear at 1-64 rows?  N alone has to fill the chip (gate_up)
 extern "C" int mi355_gemm_wide_direct_ok(const mi355_weight_t* w) {
     if (!w) return 0;                                // either activation dtype: the image entry (gemm.hip) decides
-    if (w->wkind != MI355_WKIND_INT) return 0;       // no FP8 instance
+    if (w->wkind != MI355_WKIND_INT) return 0;       // no FP8 / MXFP4 instance
     if (!((w->wbits == 4 && (w->group_size == 128 || w->group_size == 64 || w->group_size == 32)) || (w->wbits == 8 && w->group_size == 0))) return 0;
     if (w->K % 128 != 0 || w->K_pad != w->K) return 0;
     const int NT = w->N_pad / 16, TB = 10, CUS = 256;

@@ -21,9 +21,13 @@ static inline const char* mi355_kv_layout_problem(int32_t layout, int32_t kv_dty
     } while (0)
 /* Format code the GEMM launchers take in place of a bare mi355_weight_t.wbits (their `wbits` parameter): 4 / 8 / 16 for integer / 16-bit
  * weights, MI355_WFMT_FP8 for wkind = MI355_WKIND_FP8_E4M3.  A launcher without an FP8 instance matches none of its integer cases on
- * that code and returns MI355_ERR_UNSUPPORTED, so an FP8 image can never be decoded as INT8 g128 by falling through. */
-enum { MI355_WFMT_FP8 = 0x108 };
-static inline int mi355_wfmt(const mi355_weight_t* w) { return w->wkind == MI355_WKIND_FP8_E4M3 ? MI355_WFMT_FP8 : w->wbits; }
+ * that code and returns MI355_ERR_UNSUPPORTED, so an FP8 image can never be decoded as INT8 g128 by falling through.  MI355_WFMT_MXFP4
+ * (wkind = MI355_WKIND_MXFP4) works the same way: no launcher's `wbits == 4` case matches it, so an e2m1 image is never read as integer
+ * W4 g32. */
+enum { MI355_WFMT_FP8 = 0x108, MI355_WFMT_MXFP4 = 0x204 };
+static inline int mi355_wfmt(const mi355_weight_t* w) {
+    return w->wkind == MI355_WKIND_FP8_E4M3 ? MI355_WFMT_FP8 : w->wkind == MI355_WKIND_MXFP4 ? MI355_WFMT_MXFP4 : w->wbits;
+}
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -24,7 +24,7 @@ from .quant import PackedWeight
 @dataclass
 class QuantConfig:
     """Subset of rtp_llm/config/quant_config.py:281-300,641-685 that the decode path reads."""
-    method: str = "none"        # "none" | "int8" (load-time autoquant) | "gptq" | "awq" | "fp8" (e4m3, 128 x 128 block scales)
+    method: str = "none"        # "none" | "int8" (load-time autoquant) | "gptq" | "awq" | "fp8" (e4m3, 128 x 128 block scales) | "mxfp4" (e2m1, e8m0 per 32)
     bits: int = 16
     group_size: int = 0
 
@@ -123,7 +123,7 @@ class _W4A16Impl(_PackedImpl):
 
     @classmethod
     def can_handle(cls, quant_config, weight, weight_scales, hw_kernel_config=None, weight_scale_2=None, input_scale=None):
-        if weight_scales is None or weight_scales.dim() != 2:
+        if weight_scales is None or weight_scales.dim() != 2 or weight_scales.dtype == torch.uint8:   # uint8 scales: e8m0 bytes (MXFP4)
             return False
         return weight.dtype == torch.uint8 or _is_reference_w4_kernel(weight, weight_scales)
 
@@ -166,6 +166,22 @@ class _Fp8Impl(_PackedImpl):
         self._finish_init(quant.pack_fp8_block(weight.contiguous().view(torch.uint8), scales), bias)
 
 
+class _Mxfp4Impl(_PackedImpl):
+    """MXFP4 weight-only (OCP microscaling FP4, the Quark `fp4` / `e8m0` per-group-32 checkpoints), 16-bit activations.
+    weight uint8 [N, K/2] (two e2m1 codes per byte, low nibble = even input index), weight_scales uint8 e8m0 [N, K/32]."""
+
+    @classmethod
+    def can_handle(cls, quant_config, weight, weight_scales, hw_kernel_config=None, weight_scale_2=None, input_scale=None):
+        return (weight_scales is not None and weight.dtype == torch.uint8 and weight_scales.dtype == torch.uint8
+                and weight.dim() == 2 and weight_scales.dim() == 2 and weight.shape[0] == weight_scales.shape[0]
+                and weight.shape[1] * 2 == weight_scales.shape[1] * quant.MXFP4_GROUP)
+
+    def __init__(self, weight, weight_scales=None, input_scales=None, bias=None, quant_config=None, weight_scale_2=None):
+        super().__init__(weight, weight_scales, input_scales, bias, quant_config, weight_scale_2)
+        packed, self.flushed = quant.pack_mxfp4(*quant.mxfp4_from_checkpoint(weight.contiguous(), weight_scales.contiguous()))
+        self._finish_init(packed, bias)
+
+
 class Mi355F16Linear(_F16Impl, LinearBase):
     pass
 
@@ -182,8 +198,12 @@ class Mi355Fp8Linear(_Fp8Impl, LinearBase):
     pass
 
 
+class Mi355Mxfp4Linear(_Mxfp4Impl, LinearBase):
+    pass
+
+
 STRATEGY_IMPLS = (("Mi355F16Linear", _F16Impl), ("Mi355W8A16Linear", _W8A16Impl), ("Mi355W4A16Linear", _W4A16Impl),
-                  ("Mi355Fp8Linear", _Fp8Impl))
+                  ("Mi355Fp8Linear", _Fp8Impl), ("Mi355Mxfp4Linear", _Mxfp4Impl))
 
 
 class LinearFactory:
@@ -212,5 +232,5 @@ class LinearFactory:
                                  weights.get(zeros_key) if zeros_key else None)
 
 
-for _s in (Mi355F16Linear, Mi355W8A16Linear, Mi355W4A16Linear, Mi355Fp8Linear):
+for _s in (Mi355F16Linear, Mi355W8A16Linear, Mi355W4A16Linear, Mi355Fp8Linear, Mi355Mxfp4Linear):
     LinearFactory.register(_s)

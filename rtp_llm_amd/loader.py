@@ -10,6 +10,9 @@ The decode-path slice of the reference's loader stack:
   * FP8 block-quantised checkpoints (`quant_method: "fp8"`, the published form of the Qwen3 dense family): `.weight` float8_e4m3fn
     [out, in] with `.weight_scale_inv` fp32 [ceil(out/128), ceil(in/128)]; the codes are kept as they are and the block scale is
     expanded per output column (_linear_fp8), so splits and merges are plain column / 128-row operations;
+  * MXFP4 checkpoints in the Quark form (`quant_method: "quark"`, weight dtype "fp4", per_group 32, scale_format "e8m0"): `.weight`
+    uint8 [out, in/2] (low nibble = even input index) with `.weight_scale` uint8 [out, in/32]; weight-only here, the declared
+    activation quantisation is ignored (_check_quark_config, _linear_mxfp4);
   * `--quantization int8`: load-time per-channel autoquant of the fp16 linears (weight_only_quant_weight.py:94-105).
 
 With quantization="int8" the per-channel scales are computed on the full [K, N] weight BEFORE the row-parallel TP split
@@ -18,7 +21,9 @@ codes a slice of the tp = 1 codes).  bf16 / fp32 checkpoint tensors are converte
 
 Pure host code (safetensors + torch on CPU); the result feeds model.DecoderEngine / Qwen2DecoderModel unchanged.
 """
+import fnmatch
 import json
+import logging
 import os
 from typing import Dict, Optional, Tuple
 
@@ -164,6 +169,59 @@ def _linear_fp8(sh: _Shards, prefix: str, w: torch.Tensor) -> CanonLinear:
     return CanonLinear("fp8", K, N, q=codes, scales=scales, group_size=B)
 
 
+def _check_quark_config(q: dict) -> list:
+    """The Quark scheme this decode path serves: MXFP4 weights -- dtype "fp4", qscheme "per_group", group_size 32, scale_format "e8m0",
+    static, grouped along the input dimension.  Activation entries (input_tensors) must be dynamic and are ignored: weight-only.
+    Everything else is refused by the name of the field.  Returns the `exclude` patterns."""
+    g = q.get("global_quant_config")
+    if not isinstance(g, dict) or not isinstance(g.get("weight"), dict):
+        raise NotImplementedError("quantization_config.global_quant_config.weight is absent: not a Quark MXFP4 checkpoint this decode path serves")
+    w = g["weight"]
+    if w.get("dtype") != "fp4":
+        raise NotImplementedError(f"quantization_config.global_quant_config.weight.dtype={w.get('dtype')!r}: only 'fp4' (MXFP4) Quark weights are supported")
+    if w.get("qscheme") != "per_group":
+        raise NotImplementedError(f"quantization_config.global_quant_config.weight.qscheme={w.get('qscheme')!r}: only 'per_group' is supported")
+    if w.get("group_size") != quant.MXFP4_GROUP:
+        raise NotImplementedError(f"quantization_config.global_quant_config.weight.group_size={w.get('group_size')!r}: MXFP4 groups are 32 weights")
+    if w.get("scale_format") != "e8m0":
+        raise NotImplementedError(f"quantization_config.global_quant_config.weight.scale_format={w.get('scale_format')!r}: only 'e8m0' scales are supported (NVFP4 and float scales are not)")
+    if w.get("is_dynamic", False):
+        raise NotImplementedError("quantization_config.global_quant_config.weight.is_dynamic=True: weights must be quantised ahead of time")
+    if w.get("ch_axis", -1) not in (-1, 1):
+        raise NotImplementedError(f"quantization_config.global_quant_config.weight.ch_axis={w.get('ch_axis')!r}: groups must run along the input dimension (axis 1 / -1 of [out, in])")
+    it = g.get("input_tensors")
+    if it is not None and not (isinstance(it, dict) and it.get("is_dynamic", False)):
+        raise NotImplementedError("quantization_config.global_quant_config.input_tensors is not dynamic: static activation scales are not supported")
+    for k in ("desc_act", "desc"):
+        if q.get(k) or w.get(k):
+            raise NotImplementedError(f"quantization_config {k}: act-order extras are not supported with MXFP4")
+    if q.get("layer_quant_config") or q.get("layer_type_quant_config"):
+        which = "layer_quant_config" if q.get("layer_quant_config") else "layer_type_quant_config"
+        raise NotImplementedError(f"quantization_config.{which} is not empty: per-layer overrides to another scheme are not supported")
+    return list(q.get("exclude") or [])
+
+
+def _linear_mxfp4(sh: _Shards, prefix: str, w: torch.Tensor, flushed: list) -> CanonLinear:
+    """w: the module's `.weight` as read from the checkpoint, uint8 [out, in/2].  flushed: running [groups, weights] totals of the
+    exponent rule (quant.mxfp4_apply_range)."""
+    if not sh.has(prefix + ".weight_scale"):
+        raise NotImplementedError(f"{prefix}.weight_scale is missing: an MXFP4 weight needs its e8m0 group scales")
+    s = sh.get(prefix + ".weight_scale")
+    if s.dtype != torch.uint8:
+        raise NotImplementedError(f"{prefix}.weight_scale: dtype {s.dtype}, expected uint8 e8m0 bytes (float scales are not supported)")
+    N, K = w.shape[0], w.shape[1] * 2
+    if w.dim() != 2 or K % quant.MXFP4_GROUP or tuple(s.shape) != (N, K // quant.MXFP4_GROUP):
+        raise ValueError(f"{prefix}.weight_scale: shape {tuple(s.shape)}, expected ({N}, {K // quant.MXFP4_GROUP}): one byte per 32 inputs of "
+                         f"{prefix}.weight {tuple(w.shape)}")
+    try:
+        codes, sb, g, n = quant.mxfp4_apply_range(*quant.mxfp4_from_checkpoint(w, s))
+    except ValueError as e:
+        raise ValueError(f"{prefix}.weight_scale: {e}") from None
+    flushed[0] += g
+    flushed[1] += n
+    return CanonLinear("mxfp4", K, N, q=codes, scales=sb, group_size=quant.MXFP4_GROUP)
+
+
 def _cat_same_kind(parts, what: str) -> CanonLinear:
     if len({p.kind for p in parts}) != 1:
         raise NotImplementedError(f"{what}: the merged projections are stored in different formats {[p.kind for p in parts]}")
@@ -173,7 +231,7 @@ def _cat_same_kind(parts, what: str) -> CanonLinear:
 def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 1, rank: int = 0,
                        max_layers: Optional[int] = None, split_embedding: bool = False,
                        dtype: torch.dtype = torch.float16) -> Tuple[ModelConfig, Dict]:
-    """Read an HF Qwen2/Llama/Qwen3 checkpoint (fp16, GPTQ-4bit, AWQ-4bit or FP8 e4m3 with 128 x 128 block scales) into the canonical weight dict of
+    """Read an HF Qwen2/Llama/Qwen3 checkpoint (fp16, GPTQ-4bit, AWQ-4bit, FP8 e4m3 with 128 x 128 block scales or Quark MXFP4) into the canonical weight dict of
     rtp_llm_amd.model (per-rank tensors when tp > 1).  quantization="int8" autoquantises fp16 linears at load time.
     split_embedding (tp > 1): the embedding table comes back as this rank's [vocab, hidden / tp] column slice, the reference's TP
     layout (utils/model_weight.py:1490 sp_neg1) -- pair it with DecoderEngine.set_embedding_split(); default: replicated table
@@ -186,8 +244,14 @@ def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 
     fp8_skip = _check_fp8_config(cfg_json.get("quantization_config") or {}) if fp8 else set()
     if fp8 and quantization == "int8":
         raise NotImplementedError("load_hf_checkpoint: quantization='int8' on an FP8 checkpoint")
-    if not fp8 and (qc["method"] not in ("none", "gptq", "awq") or (qc["method"] != "none" and qc["bits"] != 4)):
-        raise NotImplementedError(f"quantization_config {qc} is outside the decode path of this build (4-bit GPTQ/AWQ, FP8 128 x 128 blocks)")
+    mx = qc["method"] == "quark"
+    mx_skip = _check_quark_config(cfg_json.get("quantization_config") or {}) if mx else []
+    mx_flushed = [0, 0]
+    if mx and quantization == "int8":
+        raise NotImplementedError("load_hf_checkpoint: quantization='int8' on an MXFP4 checkpoint")
+    if not fp8 and not mx and (qc["method"] not in ("none", "gptq", "awq") or (qc["method"] != "none" and qc["bits"] != 4)):
+        raise NotImplementedError(f"quantization_config {qc} is outside the decode path of this build (4-bit GPTQ/AWQ, FP8 128 x 128 blocks, "
+                                  "Quark MXFP4: fp4 per_group 32 with e8m0 scales)")
     if qc["desc_act"]:
         raise NotImplementedError("desc_act=True (act-order) GPTQ checkpoints are not supported (the reference ignores g_idx too)")
     sh = _Shards(path)
@@ -199,7 +263,20 @@ def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 
         names = {name, name[len(pre):] if pre and name.startswith(pre) else name}
         return any(n in fp8_skip or any(n.endswith("." + m) for m in fp8_skip) for n in names)
 
+    def excluded(name):        # Quark `exclude`: module names or glob patterns, with or without the "model." prefix
+        names = {name, name[len(pre):] if pre and name.startswith(pre) else name}
+        return any(n == m or n.endswith("." + m) or fnmatch.fnmatchcase(n, m) for n in names for m in mx_skip)
+
     def lin(name):
+        if mx:
+            w = sh.get(name + ".weight")
+            if excluded(name):
+                if w.dtype == torch.uint8:
+                    raise ValueError(f"{name}.weight is uint8 but the module is listed in quantization_config.exclude")
+                return _from_fp16_tensor(w, name, dtype)
+            if w.dtype != torch.uint8:
+                raise NotImplementedError(f"{name}.weight: dtype {w.dtype} in an MXFP4 checkpoint and the module is not in quantization_config.exclude")
+            return _linear_mxfp4(sh, name, w, mx_flushed)
         if fp8 and not not_converted(name):
             w = sh.get(name + ".weight")                      # read once: a module stored 16-bit falls through to _linear_fp16
             if w.dtype == torch.float8_e4m3fn:
@@ -245,6 +322,9 @@ def load_hf_checkpoint(path: str, quantization: Optional[str] = None, tp: int = 
                     raise ValueError(f"{p}self_attn.{k}.weight: shape {tuple(w.shape)}, expected ({mc.hd},) (one weight per head channel)")
                 layer[k] = w
         layers.append(split_layer_tp(layer, mc, tp, rank))
+    if mx_flushed[0]:
+        logging.getLogger(__name__).warning(
+            "MXFP4: %d groups (%d nonzero weights, each below 6 * 2^-14) had a scale below 2^-13 and were flushed to zero", *mx_flushed)
     emb = _f16(sh.get(pre + "embed_tokens.weight"), "embed_tokens", dtype)
     if sh.has("lm_head.weight"):
         head = _f16(sh.get("lm_head.weight"), "lm_head", dtype)

@@ -92,7 +92,8 @@ MODELS = {m.name: m for m in (QWEN2_7B, QWEN2_0_5B, LLAMA3_70B, QWEN2_72B, QWEN3
 @dataclass
 class CanonLinear:
     """One linear layer before packing.  kind: 'fp16' | 'int8' | 'w4' | 'fp8' (q = e4m3 bit patterns uint8 [K,N], scales = fp32
-    [ceil(K/128), N]: the checkpoint's 128 x 128 block scale expanded per column, group_size 128, no zeros)."""
+    [ceil(K/128), N]: the checkpoint's 128 x 128 block scale expanded per column, group_size 128, no zeros) | 'mxfp4' (q = e2m1
+    codes uint8 [K,N] in 0..15, scales = e8m0 bytes uint8 [K/32, N], group_size 32, no zeros)."""
     kind: str
     K: int
     N: int
@@ -112,13 +113,20 @@ class CanonLinear:
             return quant.pack_int8_per_channel(il(self.q), il(self.scales))
         if self.kind == "fp8":
             return quant.pack_fp8_block(il(self.q), il(self.scales))
+        if self.kind == "mxfp4":
+            return quant.pack_mxfp4(il(self.q), il(self.scales))[0]
         return quant.pack_groupwise_w4(il(self.q), il(self.z_eff), il(self.scales), self.group_size)
 
     def factory_weight(self) -> torch.Tensor:
         """The weight tensor as LinearFactory.create_linear takes it: the strategies tell the formats apart by dtype."""
         if self.kind == "fp16":
             return self.w
+        if self.kind == "mxfp4":   # the checkpoint form: uint8 [N, K/2], low nibble = even input index
+            return quant.mxfp4_to_checkpoint(self.q, self.scales)[0]
         return self.q.view(torch.float8_e4m3fn) if self.kind == "fp8" else self.q
+
+    def factory_scales(self) -> Optional[torch.Tensor]:
+        return self.scales.t().contiguous() if self.kind == "mxfp4" else self.scales   # mxfp4: [N, K/32] as stored
 
     def cols(self, lo: int, hi: int) -> "CanonLinear":
         """Column (output) slice — column-parallel split (sp_head / ffn_sp_neg1, utils/model_weight.py:265-277,472-509)."""
@@ -128,7 +136,7 @@ class CanonLinear:
     def rows(self, lo: int, hi: int) -> "CanonLinear":
         """Row (input) slice — row-parallel split (sp_0 / ffn_sp_0, :234-250); group aligned."""
         s = lambda t: None if t is None else t[lo:hi].contiguous()
-        if self.kind in ("w4", "fp8"):
+        if self.kind in ("w4", "fp8", "mxfp4"):
             g = self.group_size
             assert lo % g == 0 and hi % g == 0, "row split must be aligned to the quantisation group (align_size = tp*g)"
             return CanonLinear(self.kind, hi - lo, self.N, None, s(self.q), self.scales[lo // g: hi // g].contiguous(),
@@ -147,7 +155,7 @@ class CanonLinear:
         if n == 0:
             return self
         z = lambda t, k: None if t is None else torch.cat([t, torch.zeros(k, *t.shape[1:], dtype=t.dtype, device=t.device)], dim=0)
-        if self.kind in ("w4", "fp8"):   # fp8: code 0 is +0.0, z_eff stays None
+        if self.kind in ("w4", "fp8", "mxfp4"):   # fp8 / mxfp4: code 0 is +0.0, z_eff stays None (mxfp4: the packer gives a zero group byte 127)
             assert n % self.group_size == 0
             return CanonLinear(self.kind, self.K + n, self.N, None, z(self.q, n), z(self.scales, n // self.group_size),
                                z(self.z_eff, n // self.group_size), self.group_size)
@@ -180,6 +188,10 @@ def synth_linear(K: int, N: int, kind: str, device, gen: torch.Generator, group_
         w = ((torch.rand(K, N, device=device, generator=gen) * 2 - 1) * a).half()
         q, s = quant.quant_fp8_block(w)
         return CanonLinear("fp8", K, N, q=q, scales=s, group_size=quant.FP8_BLOCK)
+    if kind == "mxfp4":  # the OCP quantisation of xavier fp16 weights (K a multiple of 32)
+        w = ((torch.rand(K, N, device=device, generator=gen) * 2 - 1) * a).half()
+        q, s = quant.quant_mxfp4(w)
+        return CanonLinear("mxfp4", K, N, q=q, scales=s, group_size=quant.MXFP4_GROUP)
     G = K // group_size
     q = torch.randint(0, 16, (K, N), device=device, generator=gen, dtype=torch.uint8)
     flag = 1 if method == "gptq" else 0
@@ -366,7 +378,7 @@ class CausalAttention(nn.Module):
 
     def __init__(self, layer: Dict, cfg: Optional[ModelConfig] = None):
         super().__init__()
-        mk = lambda c, bias=None: LinearFactory.create_linear(c.factory_weight(), bias, c.scales, None, c.z_eff)
+        mk = lambda c, bias=None: LinearFactory.create_linear(c.factory_weight(), bias, c.factory_scales(), None, c.z_eff)
         self.qkv_proj, self.o_proj = mk(layer["qkv"], layer["qkv_bias"]), mk(layer["o"])
         self.qk_norm = None
         if layer.get("q_norm") is not None:
@@ -387,7 +399,7 @@ class DenseMLP(nn.Module):
 
     def __init__(self, layer: Dict):
         super().__init__()
-        mk = lambda c: LinearFactory.create_linear(c.factory_weight(), None, c.scales, None, c.z_eff)
+        mk = lambda c: LinearFactory.create_linear(c.factory_weight(), None, c.factory_scales(), None, c.z_eff)
         self.gate_up_proj, self.down_proj, self.act = mk(layer["gate_up"]), mk(layer["down"]), FusedSiluAndMul()
 
     def forward(self, x):

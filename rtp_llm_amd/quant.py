@@ -162,7 +162,7 @@ class PackedWeight:
     K_pad: int
     N_pad: int
     group_size: int                 # 0 = per-channel
-    wkind: int = 0                  # MI355_WKIND_*: 0 integer codes, 1 FP8 e4m3 bytes with an fp32 scale plane
+    wkind: int = 0                  # MI355_WKIND_*: 0 integer codes, 1 FP8 e4m3 bytes with an fp32 scale plane, 2 MXFP4 (e2m1 codes, e8m0 bytes)
 
     def to(self, device):
         return PackedWeight(self.qweight.to(device), None if self.meta is None else self.meta.to(device),
@@ -258,6 +258,100 @@ def pack_fp8_block(codes: torch.Tensor, scales: torch.Tensor) -> PackedWeight:
     meta = torch.zeros(G, N_pad, dtype=torch.float32, device=codes.device)
     meta[:, :N] = scales.float()
     return PackedWeight(x.reshape(-1).contiguous(), meta.view(torch.int32).contiguous(), 8, K, N, K_pad, N_pad, FP8_BLOCK, WKIND_FP8_E4M3)
+
+
+# --------------------------------------------------------------------------- MXFP4: e2m1 codes, e8m0 scale per 32 rows
+WKIND_MXFP4 = 2
+MXFP4_GROUP = 32
+MXFP4_E_MIN, MXFP4_E_MAX = -13, 13      # exponent range in which fp16(2^E * e2m1) is exact and normal (include/mi355_decode.h)
+E2M1_VALUES = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], dtype=torch.float32)
+
+
+def quant_mxfp4(w: torch.Tensor):
+    """[K, N] (K a multiple of 32) -> (codes uint8 [K, N] e2m1 bit patterns, scale_bytes uint8 [K/32, N] e8m0), the OCP rule per
+    32 rows of a column: E = floor(log2(amax)) - 2 (2 = the exponent of the largest e2m1 value), w / 2^E rounded to nearest even
+    onto the e2m1 grid and saturated at +-6; an all-zero group gets E = 0.  For synthetic weights and tests."""
+    K, N = w.shape
+    assert K % MXFP4_GROUP == 0, "quant_mxfp4: K must be a multiple of 32"
+    x = w.double().reshape(K // MXFP4_GROUP, MXFP4_GROUP, N)
+    amax = x.abs().amax(dim=1)
+    _, ex = torch.frexp(amax)                                    # amax = m * 2^ex, m in [0.5, 1): floor(log2 amax) = ex - 1
+    E = torch.where(amax > 0, ex.to(torch.int64) - 3, torch.zeros_like(ex, dtype=torch.int64)).clamp(-127, 127)
+    a = (x / torch.pow(2.0, E.double()).unsqueeze(1)).abs()
+    idx = torch.zeros_like(a, dtype=torch.int64)
+    for mid, up in ((0.25, False), (0.75, True), (1.25, False), (1.75, True), (2.5, False), (3.5, True), (5.0, False)):
+        idx += (a >= mid) if up else (a > mid)                   # a tie goes to the code with an even mantissa bit
+    codes = (idx + 8 * (torch.signbit(x) & (idx > 0)).to(torch.int64)).to(torch.uint8).reshape(K, N)
+    return codes.contiguous(), (E + 127).to(torch.uint8).contiguous()
+
+
+def dequant_mxfp4(codes: torch.Tensor, scale_bytes: torch.Tensor) -> torch.Tensor:
+    """codes uint8 [K, N], scale_bytes uint8 [K/32, N] -> fp32 [K, N] = e2m1(code) * 2^(byte - 127), exact."""
+    v = E2M1_VALUES.to(codes.device)[codes.long()]
+    sc = torch.pow(2.0, scale_bytes.double() - 127.0).repeat_interleave(MXFP4_GROUP, dim=0)
+    return (v.double() * sc).float()
+
+
+def mxfp4_apply_range(codes: torch.Tensor, scale_bytes: torch.Tensor):
+    """The exponent rule of the MXFP4 image (include/mi355_decode.h): returns (codes, scale_bytes, flushed_groups, flushed_weights)
+    with every group's E = byte - 127 in [-13, 13].  An all-zero group gets byte 127; a group with a nonzero code and E > 13, or
+    any byte 255 (NaN), raises ValueError; a group with E < -13 is flushed to zero codes with byte 127 (every weight in it is below
+    6 * 2^-14) and counted, with the nonzero weights it held."""
+    assert codes.dtype == torch.uint8 and scale_bytes.dtype == torch.uint8 and codes.dim() == 2
+    K, N = codes.shape
+    assert K % MXFP4_GROUP == 0 and tuple(scale_bytes.shape) == (K // MXFP4_GROUP, N), \
+        f"MXFP4: scale bytes {tuple(scale_bytes.shape)} != ({K // MXFP4_GROUP}, {N}) for codes [{K}, {N}]"
+    if bool((codes > 15).any()):
+        raise ValueError("MXFP4: a code is outside 0..15")
+    if bool((scale_bytes == 255).any()):
+        raise ValueError("MXFP4: scale byte 255 (e8m0 NaN); the exponent range of this image is E in [-13, 13]")
+    nz = ((codes & 7) != 0).reshape(K // MXFP4_GROUP, MXFP4_GROUP, N)
+    live = nz.any(dim=1)
+    E = scale_bytes.to(torch.int32) - 127
+    if bool((live & (E > MXFP4_E_MAX)).any()):
+        raise ValueError(f"MXFP4: a group scale 2^{int(E[live].max())} is outside the exponent range E in [-13, 13] "
+                         "(2^E * e2m1 must be exact in fp16)")
+    flush = live & (E < MXFP4_E_MIN)
+    groups, weights = int(flush.sum()), int((nz & flush.unsqueeze(1)).sum())
+    keep = live & ~flush
+    codes = torch.where(keep.repeat_interleave(MXFP4_GROUP, dim=0), codes, torch.zeros_like(codes))
+    scale_bytes = torch.where(keep, scale_bytes, torch.full_like(scale_bytes, 127))
+    return codes.contiguous(), scale_bytes.contiguous(), groups, weights
+
+
+def mxfp4_from_checkpoint(weight: torch.Tensor, weight_scale: torch.Tensor):
+    """The stored form -- weight uint8 [N, K/2] (low nibble = even input index), weight_scale uint8 [N, K/32] -- to
+    (codes uint8 [K, N], scale_bytes uint8 [K/32, N])."""
+    assert weight.dtype == torch.uint8 and weight_scale.dtype == torch.uint8 and weight.dim() == 2
+    N = weight.shape[0]
+    codes = torch.stack((weight & 15, weight >> 4), dim=-1).reshape(N, -1)
+    return codes.t().contiguous(), weight_scale.t().contiguous()
+
+
+def mxfp4_to_checkpoint(codes: torch.Tensor, scale_bytes: torch.Tensor):
+    """Inverse of mxfp4_from_checkpoint: (codes [K, N], scale_bytes [K/32, N]) -> (weight uint8 [N, K/2], weight_scale uint8 [N, K/32])."""
+    c = codes.t().contiguous().reshape(codes.shape[1], -1, 2)
+    return (c[..., 0] | (c[..., 1] << 4)).contiguous(), scale_bytes.t().contiguous()
+
+
+def pack_mxfp4(codes: torch.Tensor, scale_bytes: torch.Tensor):
+    """codes uint8 [K, N] (e2m1 bit patterns 0..15), scale_bytes uint8 [K/32, N] (e8m0) -> (PackedWeight, (flushed_groups,
+    flushed_weights)).  The image is the W4 tile image with code e of a k-step at bit 4e of its dword, and one meta dword per
+    (128-row chunk, column) whose byte s is the scale byte of rows 128c + 32s .. + 31 (include/mi355_decode.h, "MXFP4 weights").
+    K need only be a multiple of 32; padding holds code 0 and byte 127.  The exponent rule is mxfp4_apply_range's."""
+    codes, scale_bytes, groups, weights = mxfp4_apply_range(codes, scale_bytes)
+    K, N = codes.shape
+    K_pad, N_pad = _ceil_to(K, 128), _ceil_to(N, 16)
+    KC, NT = K_pad // 128, N_pad // 16
+    x = _pad2(codes, K_pad, N_pad, 0).reshape(KC, 4, 4, 8, NT, 16)      # [c, s, qq, e, nt, i]
+    x = x.permute(4, 0, 2, 5, 1, 3).to(torch.int64)                      # [nt, c, qq, i, s, e]
+    w = (x << (4 * torch.arange(8, device=codes.device, dtype=torch.int64))).sum(dim=-1)
+    w = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+    sb = _pad2(scale_bytes, K_pad // MXFP4_GROUP, N_pad, 127).reshape(KC, 4, N_pad).to(torch.int64)
+    m = (sb << (8 * torch.arange(4, device=codes.device, dtype=torch.int64)).reshape(1, 4, 1)).sum(dim=1)
+    m = torch.where(m >= 2 ** 31, m - 2 ** 32, m).to(torch.int32)
+    pw = PackedWeight(w.reshape(-1).contiguous(), m.contiguous(), 4, K, N, K_pad, N_pad, MXFP4_GROUP, WKIND_MXFP4)
+    return pw, (groups, weights)
 
 
 def autoquant_int8(weight_kn: torch.Tensor) -> PackedWeight:

@@ -18,12 +18,15 @@ def make_strategies(ref_linear_base) -> List[type]:
     return [type(name, (impl, ref_linear_base), {"__module__": __name__, "__doc__": impl.__doc__}) for name, impl in STRATEGY_IMPLS]
 
 
-def register(ref_linear_factory, ref_linear_base, replace_f16: bool = False, replace_fp8: bool = False) -> List[type]:
+def register(ref_linear_factory, ref_linear_base, replace_f16: bool = False, replace_fp8: bool = False,
+             replace_mxfp4: bool = False) -> List[type]:
     """Register the strategies with the reference's factory.  The fp16 strategy overlaps the reference's own ROCm fp16
     strategies (RocmF16Linear*), and the factory demands a unique match, so it is only registered when asked to replace
     them (``replace_f16``: existing fp16 strategies are removed first).  The same holds for the FP8 block-scale strategy and
     the reference's ROCm FP8 strategies (``replace_fp8``: strategies that claim a float8_e4m3fn weight with 2-D block scales
-    are removed first); by default the FP8 slot is left to the reference."""
+    are removed first); by default the FP8 slot is left to the reference.  Likewise the MXFP4 strategy (``replace_mxfp4``:
+    strategies that claim a uint8 [N, K/2] weight with uint8 e8m0 scales [N, K/32] are removed first) -- note that it is
+    weight-only, where the reference's FP4 strategies quantise the activations as well."""
     out = []
     for cls in make_strategies(ref_linear_base):
         if cls.__name__ == "Mi355F16Linear":
@@ -38,6 +41,13 @@ def register(ref_linear_factory, ref_linear_base, replace_f16: bool = False, rep
                 continue
             import torch
             probe, scales = torch.zeros(128, 128, dtype=torch.float8_e4m3fn), torch.ones(1, 1, dtype=torch.float32)
+            ref_linear_factory._strategies[:] = [s for s in ref_linear_factory._strategies
+                                                 if not _safe_can_handle(s, probe, scales)]
+        if cls.__name__ == "Mi355Mxfp4Linear":
+            if not replace_mxfp4:
+                continue
+            import torch
+            probe, scales = torch.zeros(16, 64, dtype=torch.uint8), torch.full((16, 4), 127, dtype=torch.uint8)
             ref_linear_factory._strategies[:] = [s for s in ref_linear_factory._strategies
                                                  if not _safe_can_handle(s, probe, scales)]
         ref_linear_factory.register(cls)
